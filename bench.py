@@ -1,17 +1,24 @@
 #!/usr/bin/env python3
 """Benchmark: batched convex-MPC GRF QP solves/s on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2] [--batch B] [--dump-outputs DIR] [--full]
 
 One step = one fused-kernel pass over one batch of synthetic QPs already
 resident in HBM (config 2 by default: Go1 trot, horizon 10, 1024 QPs per GPU).
 For N > 1 (launched by torch.distributed.run, one rank per GPU) each rank
 builds and solves its own shard of global indices [rank*B, (rank+1)*B): no
 data-path collective (independent QPs, weak scaling).  Rank 0 prints ONE JSON
-line with the roofline of the dominant kernel (HIP events on the launch stream),
-the max GRF error against the CPU oracle (N=1: every QP of the batch; N>1: a
-seeded sample of every rank's shard, max over ranks) and, at N=1, the CPU
-oracle timed on the host cores over the same instances.
+line.
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last
+timed step when --dump-outputs is given, and prints the headline: QP/s, ms per
+step and the HIP-event time of a launch.  --full adds everything else to the
+line: the roofline of the dominant kernel, the iteration statistics, the max GRF
+error against the CPU oracle (N=1: every QP of the batch; N>1: a seeded sample
+of every rank's shard, max over ranks), at N=1 the CPU baselines timed on the
+host cores over the same instances, and at N>1 the second timed pass that also
+gathers every GRF to rank 0.  --no-cpu, --cpu-seconds and --no-gather shape that
+part and mean nothing without --full.
 """
 from __future__ import annotations
 
@@ -49,7 +56,16 @@ def parse():
                     help="shift the global instance indices (robustness checks on other samples; recorded in config)")
     ap.add_argument("--opt", action="append", default=[], metavar="FIELD=VALUE",
                     help="set an lmpc_options field for this run (A/B of solver settings; the line records it)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: roofline, iteration statistics, parity "
+                         "against the CPU oracle, CPU baselines, the N>1 gather pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (grf, status, ipm_iters, "
+                         "polish_rounds) as DIR/<name>.npy in float64")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def host_cores():
@@ -85,6 +101,26 @@ def kernel_label(mode, riccati="lds", fused=False):
 
 def global_batch_of(strong, cfg, B, world):
     return cfg["batch"] if strong else B * world
+
+
+DUMP_MAX_BYTES = 48 << 20  # of grf.npy; status and the iteration counts add 24 bytes per QP
+
+
+def dump_outputs(out_dir, rank, grf, st, it):
+    """What solve_device handed back in the last timed step, as float64 .npy files under `out_dir`: the forces, the
+    status word and the two halves of the iteration word of every QP of this rank's shard (rank r > 0 writes
+    <name>_rank<r>.npy).  A batch whose forces exceed DUMP_MAX_BYTES is written as a fixed, seeded sample of its QPs
+    (sample_index.npy: their positions in the shard)."""
+    os.makedirs(out_dir, exist_ok=True)
+    B = grf.shape[0]
+    keep = max(1, DUMP_MAX_BYTES // (grf[0].size * 8))
+    idx = np.arange(B) if B <= keep else np.sort(np.random.default_rng(20240229).choice(B, keep, replace=False))
+    tag = "" if rank == 0 else f"_rank{rank}"
+    arrays = {"grf": grf[idx], "status": st[idx], "ipm_iters": it[idx] & 0xFFFF, "polish_rounds": it[idx] >> 16}
+    if len(idx) < B:
+        arrays["sample_index"] = idx
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{tag}.npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def main():
@@ -193,7 +229,7 @@ def main():
     # N > 1: a second timed pass, solve + grouped point-to-point gather of every rank's GRFs to
     # rank 0 (SURVEY.md 8e "with and without the gather"); reported beside `value`, never as it.
     with_gather = None
-    if dist is not None and not args.no_gather:
+    if args.full and dist is not None and not args.no_gather:
         if strong:
             counts = [b - a for a, b in (D.split_range(r, world, cfg["batch"]) for r in range(world))]
         else:
@@ -218,10 +254,50 @@ def main():
             "how": "solve + grouped isend/irecv of all GRFs to rank 0 (batch_isend_irecv over RCCL)",
         }
 
-    grf = d_grf.cpu().numpy()
-    st = d_st.cpu().numpy()
-    it = d_it.cpu().numpy()
     mode = solver.dense_path  # "ipm" (default), "gi" or "off" (H > 16, or --dense off)
+    global_batch = global_batch_of(strong, cfg, B, world)
+    total_qps = global_batch * args.steps / t_max
+    head = {
+        "metric": "QP solves/sec (Go1, horizon=10, 12 contacts); max GRF err vs exact-QP oracle",
+        "value": total_qps,
+        "unit": "QP/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "warmup_steps_run": warm_run,
+        "ms_per_step": t_max / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong" if strong else "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (Philox-seeded perturbed states, SURVEY.md 8d; generated on device)",
+        "config": {
+            "workload": wl_name if args.batch is None else f"{wl_name}@b{B}",
+            "horizon": H,
+            "batch_per_gpu": B,
+            "global_batch": global_batch,
+            "robot": cfg["robot"],
+            "gait": "mixed" if cfg["gait"] < 0 else ["trot", "crawl", "trot_with_stand", "stand"][cfg["gait"]],
+            "terrain": f"per-leg normals, tilt U(0, {synth.TERRAIN_THETA_MAX}) rad" if terrain else None,
+            "parallelism": f"dp{world} (independent QP shards, no collective)",
+            **({"options": opts} if opts else {}),
+            **({"index_offset": args.index_offset} if args.index_offset else {}),
+        },
+    }
+    if args.dump_outputs is not None or args.full:
+        grf = d_grf.cpu().numpy()
+        st = d_st.cpu().numpy()
+        it = d_it.cpu().numpy()
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, rank, grf, st, it)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps({**head, "kernel_ms": kernel_ms, "dense_path": mode, "riccati_path": args.riccati}),
+                  flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     ipm_mean = float(np.mean(it & 0xFFFF))
     pol_mean = float(np.mean(it >> 16))
     con_host = d_con.cpu().numpy()
@@ -253,8 +329,6 @@ def main():
     useful_tf = useful_per_qp * B / (kernel_ms * 1e-3) / 1e12
     headline_contract = mode != "off" and dense_qp.all()  # every QP on a condensed dense kernel (config 2)
     achieved_tf = (contract_per_qp if headline_contract else useful_per_qp) * B / (kernel_ms * 1e-3) / 1e12
-    global_batch = global_batch_of(strong, cfg, B, world)
-    total_qps = global_batch * args.steps / t_max
 
     stats = D.sum_over_ranks([(st == 0).sum(), (st == 1).sum(), (st == 2).sum()], dist, dev)
 
@@ -371,31 +445,7 @@ def main():
 
     if rank == 0:
         line = {
-            "metric": "QP solves/sec (Go1, horizon=10, 12 contacts); max GRF err vs exact-QP oracle",
-            "value": total_qps,
-            "unit": "QP/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "warmup_steps_run": warm_run,
-            "ms_per_step": t_max / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong" if strong else "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic (Philox-seeded perturbed states, SURVEY.md 8d; generated on device)",
-            "config": {
-                "workload": wl_name if args.batch is None else f"{wl_name}@b{B}",
-                "horizon": H,
-                "batch_per_gpu": B,
-                "global_batch": global_batch,
-                "robot": cfg["robot"],
-                "gait": "mixed" if cfg["gait"] < 0 else ["trot", "crawl", "trot_with_stand", "stand"][cfg["gait"]],
-                "terrain": f"per-leg normals, tilt U(0, {synth.TERRAIN_THETA_MAX}) rad" if terrain else None,
-                "parallelism": f"dp{world} (independent QP shards, no collective)",
-                **({"options": opts} if opts else {}),
-                **({"index_offset": args.index_offset} if args.index_offset else {}),
-            },
+            **head,
             "roofline": {
                 # fp64 compute, not HBM: a latency-bound wave per QP issuing fp64 VALU and MFMA work;
                 # the fp64 peak is the same for both.  achieved / frac: SURVEY.md 8(d)'s contract flops where every QP

@@ -9,7 +9,7 @@ for tag in "$@"; do
     cfg=${1%gi}; cfg=${cfg%off}; steps=$2
     dense=""
     case "$1" in *gi) dense="--dense gi";; *off) dense="--dense off";; esac
-    out=$(LMPC_LIB=tools/build/liblmpc_$tag.so timeout -k 10 120 python bench.py $AB_ARGS $dense --config $cfg --steps $steps --warmup 2 --no-cpu 2>/dev/null) || { echo "$tag config $1 FAILED"; exit 1; }
+    out=$(LMPC_LIB=tools/build/liblmpc_$tag.so timeout -k 10 120 python bench.py --full $AB_ARGS $dense --config $cfg --steps $steps --warmup 2 --no-cpu 2>/dev/null) || { echo "$tag config $1 FAILED"; exit 1; }
     echo "$out" | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$tag', 'config', '$1', 'kernel_ms %.4f'%d['roofline']['kernel_ms'], 'QP/s %.3e'%d['value'], 'err %.1e'%d['max_grf_err'], d['qp_status'])"
   done
 done

@@ -9,7 +9,7 @@ for lib in ${AB_LIBS:-product}; do
 for spec in ${AB_CFGS:-2:ipm:100}; do IFS=: read c d steps <<< "$spec"
  for set in "${SETS[@]}"; do
   args=""; IFS=',' read -ra kv <<< "$set"; for x in "${kv[@]}"; do args="$args --opt $x"; done
-  timeout -k 10 120 python bench.py --config $c --dense $d --steps $steps --warmup 3 --no-cpu --index-offset $off $args 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$lib cfg $c/$d off $off [$set]', 'kernel_ms %.4f'%d['roofline']['kernel_ms'], 'err %.1e'%d['max_grf_err'], d['qp_status'], 'ipm %.2f rounds %.2f'%(d['ipm_iters_mean'], d['polish_rounds_mean']))" || exit 1
+  timeout -k 10 120 python bench.py --full --config $c --dense $d --steps $steps --warmup 3 --no-cpu --index-offset $off $args 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$lib cfg $c/$d off $off [$set]', 'kernel_ms %.4f'%d['roofline']['kernel_ms'], 'err %.1e'%d['max_grf_err'], d['qp_status'], 'ipm %.2f rounds %.2f'%(d['ipm_iters_mean'], d['polish_rounds_mean']))" || exit 1
  done
 done
 done

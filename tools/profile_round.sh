@@ -17,12 +17,12 @@ steps_of() { case $1 in 2) echo "--steps 20 --warmup 3";; 4) echo "--steps 5 --w
 psteps_of() { case $1 in 2) echo "--steps 5 --warmup 1";; *) echo "--steps 2 --warmup 1";; esac; }
 rc=0
 for c in $CFGS; do
-  rp --kernel-trace --stats -d $OUT/c$c -o c$c --output-format csv -- python3 bench.py --config $c $(steps_of $c) --no-cpu > $OUT/c${c}_bench.log 2>&1 || { rc=$?; break; }
-  pmc --pmc FETCH_SIZE --kernel-trace -d $OUT/f$c -o f$c --output-format csv -- python3 bench.py --config $c $(psteps_of $c) --no-cpu > $OUT/f$c.log 2>&1 || { rc=$?; break; }
-  pmc --pmc WRITE_SIZE --kernel-trace -d $OUT/w$c -o w$c --output-format csv -- python3 bench.py --config $c $(psteps_of $c) --no-cpu > $OUT/w$c.log 2>&1 || { rc=$?; break; }
-  pmc --pmc SQ_INSTS_VALU_FLOPS_FP64 SQ_INSTS_VALU_MFMA_MOPS_F64 --kernel-trace -d $OUT/q$c -o q$c --output-format csv -- python3 bench.py --config $c $(psteps_of $c) --no-cpu > $OUT/q$c.log 2>&1 || { rc=$?; break; }
+  rp --kernel-trace --stats -d $OUT/c$c -o c$c --output-format csv -- python3 bench.py --full --config $c $(steps_of $c) --no-cpu > $OUT/c${c}_bench.log 2>&1 || { rc=$?; break; }
+  pmc --pmc FETCH_SIZE --kernel-trace -d $OUT/f$c -o f$c --output-format csv -- python3 bench.py --full --config $c $(psteps_of $c) --no-cpu > $OUT/f$c.log 2>&1 || { rc=$?; break; }
+  pmc --pmc WRITE_SIZE --kernel-trace -d $OUT/w$c -o w$c --output-format csv -- python3 bench.py --full --config $c $(psteps_of $c) --no-cpu > $OUT/w$c.log 2>&1 || { rc=$?; break; }
+  pmc --pmc SQ_INSTS_VALU_FLOPS_FP64 SQ_INSTS_VALU_MFMA_MOPS_F64 --kernel-trace -d $OUT/q$c -o q$c --output-format csv -- python3 bench.py --full --config $c $(psteps_of $c) --no-cpu > $OUT/q$c.log 2>&1 || { rc=$?; break; }
   if [ "$c" = 2 ]; then
-    rp --kernel-trace --stats -d $OUT/c2gi -o c2gi --output-format csv -- python3 bench.py --dense gi --steps 20 --warmup 3 --no-cpu > $OUT/c2gi_bench.log 2>&1 || { rc=$?; break; }
+    rp --kernel-trace --stats -d $OUT/c2gi -o c2gi --output-format csv -- python3 bench.py --full --dense gi --steps 20 --warmup 3 --no-cpu > $OUT/c2gi_bench.log 2>&1 || { rc=$?; break; }
   fi
 done
 if [ $rc = 0 ]; then

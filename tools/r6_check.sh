@@ -5,7 +5,7 @@ OUT=gpurun_out/r6
 mkdir -p $OUT
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > $OUT/gpu_tests.log 2>&1 &&
 timeout -k 10 300 python -c "import __graft_entry__ as G; G.smoke()" > $OUT/smoke.log 2>&1 &&
-timeout -k 10 300 python bench.py --steps 50 --warmup 5 > $OUT/bench_c2.json 2> $OUT/bench_c2.err &&
+timeout -k 10 300 python bench.py --full --steps 50 --warmup 5 > $OUT/bench_c2.json 2> $OUT/bench_c2.err &&
 timeout -k 10 120 python tools/step_overhead.py 300 2 > $OUT/overhead.log 2>&1
 rc=$?
 tail -2 $OUT/gpu_tests.log; cat $OUT/smoke.log; cat $OUT/overhead.log

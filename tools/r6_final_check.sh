@@ -7,7 +7,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout
 timeout -k 10 300 python -c "import __graft_entry__ as G; G.smoke()" > $OUT/smoke.log 2>&1 &&
 timeout -k 10 200 python tools/fuzz_parity.py --seconds 75 --batch 512 --out $OUT/fuzz_b512.json > $OUT/fuzz_b512.log 2>&1 &&
 timeout -k 10 200 python tools/fuzz_parity.py --seconds 75 --batch 2048 --out $OUT/fuzz_b2048.json > $OUT/fuzz_b2048.log 2>&1 &&
-timeout -k 10 300 python bench.py --config 3 --steps 10 --warmup 3 --no-cpu > $OUT/bench_c3.json 2> $OUT/bench_c3.err
+timeout -k 10 300 python bench.py --full --config 3 --steps 10 --warmup 3 --no-cpu > $OUT/bench_c3.json 2> $OUT/bench_c3.err
 rc=$?
 tail -2 $OUT/gpu_tests.log; cat $OUT/smoke.log | grep -v amdgpu
 python -c "

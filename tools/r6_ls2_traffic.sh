@@ -10,7 +10,7 @@ for rep in 1 2; do
 done
 for tag in ls2h3 ls2h2 ls2h0 prod6; do
   for ctr in FETCH_SIZE WRITE_SIZE; do
-    LMPC_LIB=tools/build/liblmpc_$tag.so timeout -s KILL 240 rocprofv3 --pmc $ctr --kernel-trace -d $OUT/${tag}_$ctr -o p --output-format csv -- python3 bench.py --config 3 --steps 2 --warmup 1 --warmup-ms 0 --no-cpu > $OUT/${tag}_$ctr.log 2>&1 || exit 4
+    LMPC_LIB=tools/build/liblmpc_$tag.so timeout -s KILL 240 rocprofv3 --pmc $ctr --kernel-trace -d $OUT/${tag}_$ctr -o p --output-format csv -- python3 bench.py --full --config 3 --steps 2 --warmup 1 --warmup-ms 0 --no-cpu > $OUT/${tag}_$ctr.log 2>&1 || exit 4
   done
 done
 python3 - << 'PY'

@@ -5,8 +5,8 @@ export TMPDIR=/tmp
 OUT=gpurun_out/tol
 mkdir -p $OUT
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > $OUT/gpu_tests.log 2>&1 &&
-timeout -k 10 300 python bench.py > $OUT/bench_c2.json 2> $OUT/bench_c2.err &&
-for c in 3 4 5; do timeout -k 10 300 python bench.py --config $c --steps 10 --warmup 3 --no-cpu > $OUT/bench_c$c.json 2> $OUT/bench_c$c.err || exit 3; done &&
+timeout -k 10 300 python bench.py --full > $OUT/bench_c2.json 2> $OUT/bench_c2.err &&
+for c in 3 4 5; do timeout -k 10 300 python bench.py --full --config $c --steps 10 --warmup 3 --no-cpu > $OUT/bench_c$c.json 2> $OUT/bench_c$c.err || exit 3; done &&
 timeout -k 10 300 python -u tools/fuzz_parity.py --seconds 120 --batch 512 --out $OUT/fuzz_b512.json > $OUT/fuzz_b512.log 2>&1 &&
 timeout -k 10 300 python -u tools/fuzz_parity.py --seconds 120 --batch 1024 --out $OUT/fuzz_b1024.json > $OUT/fuzz_b1024.log 2>&1
 rc=$?

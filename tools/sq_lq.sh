@@ -12,7 +12,7 @@ rc=0
 for path in ${SQ_PATHS:-lds scratch}; do
   for set in A B; do
     C=${!set}
-    timeout -s KILL 120 rocprofv3 --pmc $C --kernel-trace -d $OUT/$path$set -o $path$set --output-format csv -- python3 bench.py $CFG --riccati $path --steps 2 --warmup 1 --no-cpu > $OUT/$path$set.log 2>&1 || { rc=$?; break 2; }
+    timeout -s KILL 120 rocprofv3 --pmc $C --kernel-trace -d $OUT/$path$set -o $path$set --output-format csv -- python3 bench.py --full $CFG --riccati $path --steps 2 --warmup 1 --no-cpu > $OUT/$path$set.log 2>&1 || { rc=$?; break 2; }
   done
 done
 echo "sq_lq rc=$rc"

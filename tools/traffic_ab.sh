@@ -7,7 +7,7 @@ mkdir -p $OUT
 args=$1; shift
 for tag in "$@"; do
   for c in FETCH_SIZE WRITE_SIZE; do
-    LMPC_LIB=tools/build/liblmpc_$tag.so timeout -s KILL 240 rocprofv3 --pmc $c --kernel-trace -d $OUT/$tag$c -o $tag$c --output-format csv -- python3 bench.py $args --steps 2 --warmup 1 --no-cpu > $OUT/$tag$c.log 2>&1 || { echo "$tag $c FAILED"; exit 1; }
+    LMPC_LIB=tools/build/liblmpc_$tag.so timeout -s KILL 240 rocprofv3 --pmc $c --kernel-trace -d $OUT/$tag$c -o $tag$c --output-format csv -- python3 bench.py --full $args --steps 2 --warmup 1 --no-cpu > $OUT/$tag$c.log 2>&1 || { echo "$tag $c FAILED"; exit 1; }
   done
 done
 echo "traffic_ab done"

@@ -181,13 +181,9 @@ __device__ unsigned long long lmpc_condense_stamps[4096][5];
 #define CSTAMP(i) do {} while (0)
 #define CSTAMP_DECL
 #endif
-// 1: the H-column pass keeps G0's rows 0-2 in registers on flat ground (round 5: H columns 21.3 k -> 17.1 k cycles
-// per QP, config 2 -0.7 %, profiles/r05/border/ab_hoist_g0.log); 0: LDS loads in the loop (the compiler cannot hoist
-// them past the H stores, which may alias).  Loading the step's yaw terms one iteration ahead here and in the free
-// response changed neither phase's cycles and was not kept.
-#ifndef LMPC_COND_HOIST_G0
-#define LMPC_COND_HOIST_G0 1
-#endif
+// The H-column pass keeps G0's rows 0-2 in registers on flat ground (round 5: H columns 21.3 k -> 17.1 k cycles per
+// QP, config 2 -0.7 % against LDS loads in the loop, profiles/r05/border/ab_hoist_g0.log).  Loading the step's yaw
+// terms one iteration ahead here and in the free response changed neither phase's cycles and was not kept.
 template <bool TERRAIN>
 __device__ __forceinline__ void dense_condense(const DevParams& prm, const DSmem& S, int H, int nls,
                                                unsigned long long smask, int lane) {
@@ -339,7 +335,6 @@ __device__ __forceinline__ void dense_condense(const DevParams& prm, const DSmem
             }
         }
         const int vkk = vvalid ? vk : -1;  // padding / unused lanes take part in no step
-#if LMPC_COND_HOIST_G0
         // flat ground: rows 0-2 of G0 in registers (loop-invariant; in the loop they are LDS loads the compiler cannot
         // hoist past the H stores, which may alias)
         double g0r[3][12];
@@ -349,7 +344,6 @@ __device__ __forceinline__ void dense_condense(const DevParams& prm, const DSmem
 #pragma unroll
                 for (int c = 0; c < 12; ++c) g0r[q][c] = S.G0[q * 12 + c];
         }
-#endif
         for (int i = H - 1; i >= 0; --i) {
             if (i < vkk) {  // L <- A_{i+1}' L
                 const double ck = S.cs[2 * (i + 1)], sk = S.cs[2 * (i + 1) + 1];
@@ -377,13 +371,8 @@ __device__ __forceinline__ void dense_condense(const DevParams& prm, const DSmem
 #pragma unroll
                             for (int q = 0; q < 6; ++q) val = fma(S.G0[q * 12 + cp], L[6 + q], val);
                         } else {  // flat ground: rows 3-5 of G0 are dt/m I (dense_prologue) -- the same sum, bit for bit
-#if LMPC_COND_HOIST_G0
 #pragma unroll
                             for (int q = 0; q < 3; ++q) val = fma(g0r[q][cp], L[6 + q], val);
-#else
-#pragma unroll
-                            for (int q = 0; q < 3; ++q) val = fma(S.G0[q * 12 + cp], L[6 + q], val);
-#endif
                             val = fma(dtm, L[9 + ap], val);
                         }
                         if (bp == vb) val += rbl[ap];
@@ -420,21 +409,11 @@ __device__ __forceinline__ void dense_condense(const DevParams& prm, const DSmem
 struct DiagInv {
     d4 ui, uit;
 };
-// 1: the 3x3 pivot's reciprocals one after another instead of from the leading minors (diagnostic A/B)
-#ifndef LMPC_DIAG_SEQ_RSQ
-#define LMPC_DIAG_SEQ_RSQ 0
-#endif
 // Inlined at its call sites (round 3): outlined, the call cost the caller ~1.7 k cycles per tile in argument /
 // result moves and in the caller-saved registers it had to park around the call (5.6 k cycles per tile in the
 // kernel vs 3.9 k alone, tools/ubench/diag_parts.hip); inlined, config 2 runs 2 % faster (0.2304 -> 0.2259 ms,
-// tools/ab_bench.sh, two alternating runs each; bit-identical results).  -DLMPC_DIAG_OUTLINE (diagnostic builds
-// only) restores the call.
-#ifdef LMPC_DIAG_OUTLINE
-#define LMPC_DIAG_ATTR noinline
-#else
-#define LMPC_DIAG_ATTR always_inline
-#endif
-static __device__ __attribute__((LMPC_DIAG_ATTR)) DiagInv diag_inverse(ldouble* scr, d4 M, int amask, int lane) {
+// tools/ab_bench.sh, two alternating runs each; bit-identical results).
+static __device__ __attribute__((always_inline)) DiagInv diag_inverse(ldouble* scr, d4 M, int amask, int lane) {
     amask = __builtin_amdgcn_readfirstlane(amask);  // uniform (tile_mask), but arguments arrive in VGPRs
     // staging of the registers that hold the pivot rows (i0, i1): every lane stores its value unconditionally, so
     // row r of register i sits at 16 (r & 3) + c (+64 for i1) -- static read offsets, no per-lane address select
@@ -473,15 +452,9 @@ static __device__ __attribute__((LMPC_DIAG_ATTR)) DiagInv diag_inverse(ldouble* 
         const double w0 = sW[so(0) + c], w1 = sW[so(1) + c], w2 = sW[so(2) + c];  // W[o+a][c]
         // P = L_p L_p' with the three pivot reciprocals from the leading minors, so their rsq chains run side by
         // side instead of one after the other: d1 = m11 / p00, d2 = det / m11 (m11 = p00 p11 - p10^2), hence
-        // 1/sqrt(d1) = sqrt(p00) rsq(m11) and 1/sqrt(d2) = sqrt(m11) rsq(det)
-#if LMPC_DIAG_SEQ_RSQ
-        // the pivots one after another (12 fewer fp64 instructions, two more rsq latencies on the chain)
-        const double i00 = rsq_nr(p00);
-        const double l10 = p10 * i00, l20 = p20 * i00;
-        const double i11 = rsq_nr(fma(-l10, l10, p11));
-        const double l21 = fma(-l20, l10, p21) * i11;
-        const double i22 = rsq_nr(fma(-l21, l21, fma(-l20, l20, p22)));
-#else
+        // 1/sqrt(d1) = sqrt(p00) rsq(m11) and 1/sqrt(d2) = sqrt(m11) rsq(det).  (The pivots one after another: 12
+        // fewer fp64 instructions, two more rsq latencies on the chain, 1.5 % slower on the dual active set -- DESIGN.md
+        // 4b, v19.)
         const double m11 = fma(p00, p11, -p10 * p10);
         const double c00 = fma(p11, p22, -p21 * p21), c01 = fma(p10, p22, -p21 * p20), c02 = fma(p10, p21, -p11 * p20);
         const double det = fma(p00, c00, fma(-p10, c01, p20 * c02));
@@ -490,7 +463,6 @@ static __device__ __attribute__((LMPC_DIAG_ATTR)) DiagInv diag_inverse(ldouble* 
         const double i11 = (p00 * i00) * r1;
         const double l21 = fma(-l20, l10, p21) * i11;
         const double i22 = (m11 * r1) * r2;
-#endif
         // row c of L_C (zero in and above the pivot rows)
         const double x0 = t0 * i00;
         const double x1 = fma(-l10, x0, t1) * i11;

@@ -21,69 +21,35 @@
 #define DSTAMP_FLUSH(qp) do {} while (0)
 #endif
 
-// Range-space (Schur complement) polish rounds after a factorised one (dense_body): 1 on, 0 every round refactors;
-// LMPC_SCHUR_KMAX added face rows at most per update
+// Range-space (Schur complement) polish rounds after a factorised one (dense_body): 1 on, 0 every round refactors
+// (the test-only "noschur" build, tests/test_gpu_kkt.py)
 #ifndef LMPC_POLISH_SCHUR
 #define LMPC_POLISH_SCHUR 1
 #endif
-#ifndef LMPC_SCHUR_KMAX
-#define LMPC_SCHUR_KMAX 6
-#endif
-// ... including rounds that drop factorised faces (new columns: the bordered system); 0: only rounds that add faces
-// cost rule in half-units of one solve: 2 per entry, LMPC_SCHUR_CW2 more per column (its matvec), LMPC_SCHUR_SLOPE2
-// per diagonal tile a refactorisation would keep, at most LMPC_SCHUR_LIM2
-#ifndef LMPC_SCHUR_CW2
-#define LMPC_SCHUR_CW2 0
-#endif
-#ifndef LMPC_SCHUR_SLOPE2
-#define LMPC_SCHUR_SLOPE2 4
-#endif
-#ifndef LMPC_SCHUR_LIM2
-#define LMPC_SCHUR_LIM2 10
-#endif
-// interior-point start: z = LMPC_DENSE_Z0 / s (complementarity LMPC_DENSE_Z0 per pair)
-#ifndef LMPC_DENSE_Z0
-#define LMPC_DENSE_Z0 1.0
-#endif
-#ifndef LMPC_POLISH_BORDER
-#define LMPC_POLISH_BORDER 1
-#endif
-// Gondzio centrality correctors per interior-point iteration (0: none, the product; diagnostic A/B)
-#ifndef LMPC_GONDZIO
-#define LMPC_GONDZIO 0
-#endif
-#ifndef LMPC_GZ_SKIP
-#define LMPC_GZ_SKIP 0.9
-#endif
-#ifndef LMPC_GZ_DA
-#define LMPC_GZ_DA 0.2
-#endif
-#ifndef LMPC_GZ_GAMMA
-#define LMPC_GZ_GAMMA 0.1
-#endif
-#ifndef LMPC_GZ_BMIN
-#define LMPC_GZ_BMIN 0.1
-#endif
-#ifndef LMPC_GZ_BMAX
-#define LMPC_GZ_BMAX 10.0
-#endif
-// one step of iterative refinement of a verified range-space round whose stationarity residual is above
-// LMPC_REFINE_SR of the gradient scale, certified again (round 6); 0: the update as is.  Over 8192 config-2 QPs
-// (tools/refine_diag.py, profiles/r06/refine/) 1857 end on a range-space round; their residuals are <= 6.2e-13 of
-// gscale except one at 3.4e-12 -- the QP whose forces sat 1.8e-9 from the optimum (the others' corrections <= 3e-10).
-// Refining every such QP cost config 2 +3.4 %; this trigger refines that one.
-#ifndef LMPC_POLISH_REFINE
-#define LMPC_POLISH_REFINE 1
-#endif
-#ifndef LMPC_REFINE_SR
-#ifdef LMPC_REFINE_DIAG
-#define LMPC_REFINE_SR 0.0
-#else
-#define LMPC_REFINE_SR 1e-12
-#endif
-#endif
 
 namespace lmpc {
+
+// A range-space round adds face rows and, where it drops factorised faces, new columns (the bordered system),
+// LMPC_SCHUR_KMAX entries at most.  Cost rule in half-units of one solve: 2 per entry, LMPC_SCHUR_SLOPE2 per diagonal
+// tile a refactorisation would keep, at most LMPC_SCHUR_LIM2 (config 2 0.1827 -> 0.1731 ms against accepting every
+// qualifying round; rows-only rounds and a further charge per column's matvec were tried and dropped: DESIGN.md,
+// "Experiments removed from the source").
+constexpr int LMPC_SCHUR_KMAX = 6;
+constexpr int LMPC_SCHUR_SLOPE2 = 4;
+constexpr int LMPC_SCHUR_LIM2 = 10;
+// interior-point start: z = LMPC_DENSE_Z0 / s (complementarity LMPC_DENSE_Z0 per pair); 0.3 and 3 ran config 2 in
+// 0.212 / 0.201 ms against 0.174 (profiles/r05, ab_z0.log)
+constexpr double LMPC_DENSE_Z0 = 1.0;
+// A verified range-space round whose stationarity residual is above LMPC_REFINE_SR of the gradient scale takes one
+// step of iterative refinement and is certified again (round 6).  Over 8192 config-2 QPs (tools/refine_diag.py,
+// profiles/r06/refine/) 1857 end on a range-space round; their residuals are <= 6.2e-13 of gscale except one at
+// 3.4e-12 -- the QP whose forces sat 1.8e-9 from the optimum (the others' corrections <= 3e-10).  Refining every such
+// QP cost config 2 +3.4 %; this trigger refines that one.  tools/refine_diag.py's build refines every round.
+#ifdef LMPC_REFINE_DIAG
+constexpr double LMPC_REFINE_SR = 0.0;
+#else
+constexpr double LMPC_REFINE_SR = 1e-12;
+#endif
 
 // range-space rounds' scratch (S.scr): h_matvec 0..47, entries U / uleg / utyp / Cb 48..119, the round's s 120..125
 // (for its refinement) and K's smallest pivot ratio 126, W = M^-1 V and the columns' V from 128
@@ -131,9 +97,6 @@ __device__ __forceinline__ SchurLeg schur_leg(bool chg, int act, int bact, bool 
     // the factorised particular solution must lie in the kept space: no f_max face at an apex on either side
     r.ok = r.kc >= 0 && r.kc <= 3 && r.kr <= 3 && (!bap || !(cm & 16)) && (!nap || !((act | bact) & 16)) &&
            (nap || nn == nc - r.kr);
-#if !LMPC_POLISH_BORDER
-    r.ok = r.ok && r.kc == 0 && !nap && !bap;
-#endif
     return r;
 }
 
@@ -379,7 +342,7 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
                 const unsigned long long dif = __ballot(st && act != bact);
                 const int kt = dif ? (__ffsll((long long)dif) - 1) / 5 : 4;
                 schur = __all(sl.ok) && nsch + ncol <= LMPC_SCHUR_KMAX &&
-                        2 * nsch + LMPC_SCHUR_CW2 * ncol + LMPC_SCHUR_SLOPE2 * kt <= LMPC_SCHUR_LIM2;
+                        2 * nsch + LMPC_SCHUR_SLOPE2 * kt <= LMPC_SCHUR_LIM2;
             }
             // a factorised round: tiles ahead of the first leg-step whose faces differ from the last factorised
             // round's keep their factors
@@ -813,13 +776,11 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
                     for (int p = 0; p < 3; ++p) du[p] = fma(U[4 * j + p], sv[j], du[p]);
                 }
             }
-#if LMPC_POLISH_REFINE
             if (lane == 0) {  // s of this round, for the refinement of a verified round (polish verification below)
 #pragma unroll
                 for (int j = 0; j < KM; ++j) S.scr[DN_SCHUR_SV + j] = sv[j];
                 S.scr[DN_SCHUR_SV + KM] = kmin;
             }
-#endif
             // a rank-deficient update (rounding): keep y0; the round will not verify and the next one refactorises
             // the same faces (a settled set that fails right after a range-space round, below)
             S.vec[lane] = bad ? S.lua[lane] : yv;
@@ -904,83 +865,8 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
                     if (dz[i] < 0.0) dmax = fmin(dmax, -z[i] * __builtin_amdgcn_rcp(dz[i]));
                 }
             }
-#if LMPC_SPLIT_STEP
-#if LMPC_GONDZIO
-            double alpha = fmin(1.0, LMPC_STEP_FRAC * wave_min(amax));
-            double alpd = fmin(1.0, LMPC_STEP_FRAC * wave_min(dmax));
-#else
             const double alpha = fmin(1.0, LMPC_STEP_FRAC * wave_min(amax));
             const double alpd = fmin(1.0, LMPC_STEP_FRAC * wave_min(dmax));
-#endif
-#else
-            const double alpha = fmin(1.0, LMPC_STEP_FRAC * wave_min(fmin(amax, dmax))), alpd = alpha;
-#endif
-#if LMPC_GONDZIO && LMPC_SPLIT_STEP
-            // Gondzio's multiple centrality correctors (diagnostic A/B): while the step is short,
-            // pull the complementarity products of the trial point at a longer step into [bmin, bmax] x sigma mu and
-            // re-solve with the factorisation in hand; keep the new direction if its step is longer by gamma x delta
-            for (int gk = 0; gk < LMPC_GONDZIO; ++gk) {
-                const double am = fmin(alpha, alpd);
-                if (am >= LMPC_GZ_SKIP) break;  // wave-uniform
-                const double tp = fmin(1.0, alpha + LMPC_GZ_DA), td = fmin(1.0, alpd + LMPC_GZ_DA);
-                const double lo = LMPC_GZ_BMIN * smu, hi = LMPC_GZ_BMAX * smu;
-                double rg[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, dsaz[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-                double rtg[3] = {0.0, 0.0, 0.0};
-                if (st) {
-                    double oa[5], ua[3], wg[5];
-#pragma unroll
-                    for (int m = 0; m < 3; ++m) ua[m] = S.lua[3 * lane + m];
-                    cons_resid(ua, mu, fzmax, oa);
-#pragma unroll
-                    for (int i = 0; i < 5; ++i) {
-                        const double dsa = -oa[i] - s[i];
-                        const double dza = -z[i] - z[i] * is[i] * dsa;
-                        dsaz[i] = dsa * dza;
-                        const double v = (s[i] + tp * ds[i]) * (z[i] + td * dz[i]);
-                        const double r = v < lo ? lo - v : (v > hi ? fmax(hi - v, -hi) : 0.0);
-                        rg[i] = r;
-                        wg[i] = (z[i] * (s[i] - (i == 4 ? fzmax : 0.0)) + smu + r - dsaz[i]) * is[i];
-                    }
-                    cons_tw(wg, mu, rtg);
-                }
-                LMPC_SYNC();
-                if (st) {
-#pragma unroll
-                    for (int a = 0; a < 3; ++a) S.vec[vidx(lane, a)] = -(S.gv[vidx(lane, a)] + rtg[a]);
-                }
-                LMPC_SYNC();
-                solve_vec();
-                double ug[3] = {0.0, 0.0, 0.0}, dsg[5], dzg[5];
-                double amg = 1.0, dmg = 1.0;
-#pragma unroll
-                for (int i = 0; i < 5; ++i) dsg[i] = dzg[i] = 0.0;
-                if (st) {
-                    double o[5];
-#pragma unroll
-                    for (int a = 0; a < 3; ++a) ug[a] = S.vec[vidx(lane, a)];
-                    cons_resid(ug, mu, fzmax, o);
-#pragma unroll
-                    for (int i = 0; i < 5; ++i) {
-                        dsg[i] = -o[i] - s[i];
-                        dzg[i] = (smu + rg[i] - z[i] * s[i] - dsaz[i] - z[i] * dsg[i]) * is[i];
-                        if (dsg[i] < 0.0) amg = fmin(amg, -s[i] * __builtin_amdgcn_rcp(dsg[i]));
-                        if (dzg[i] < 0.0) dmg = fmin(dmg, -z[i] * __builtin_amdgcn_rcp(dzg[i]));
-                    }
-                }
-                const double ag = fmin(1.0, LMPC_STEP_FRAC * wave_min(amg));
-                const double adg = fmin(1.0, LMPC_STEP_FRAC * wave_min(dmg));
-                if (!(fmin(ag, adg) >= am + LMPC_GZ_GAMMA * LMPC_GZ_DA)) break;
-                alpha = ag;
-                alpd = adg;
-#pragma unroll
-                for (int m = 0; m < 3; ++m) u[m] = ug[m];
-#pragma unroll
-                for (int i = 0; i < 5; ++i) {
-                    ds[i] = dsg[i];
-                    dz[i] = dzg[i];
-                }
-            }
-#endif
             if (st) {
 #pragma unroll
                 for (int m = 0; m < 3; ++m) f[m] += alpha * (u[m] - f[m]);
@@ -1065,7 +951,7 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
                 if (sr <= prm.tol_d * gscale)
 #endif
                 {
-#if LMPC_POLISH_SCHUR && LMPC_POLISH_REFINE
+#if LMPC_POLISH_SCHUR
                     if (schur && sr > LMPC_REFINE_SR * gscale) {
                         // One step of iterative refinement of a verified range-space round.  The
                         // update solves the round's bordered system [M V; V' Cb] [y; s] = [r0; c] through K = Cb - V'W,

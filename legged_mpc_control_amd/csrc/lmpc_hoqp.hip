@@ -64,38 +64,8 @@ __device__ unsigned long long lmpc_hoqp_substamps[4096][8];
 #define HSTAMP_FLUSH(b) do {} while (0)
 #endif
 
-// Diagnostic builds only (tools/build, -DHQ_INL_<helper>): that per-iteration helper inlined instead of outlined
-// (A/B of the call overhead against register pressure, tools/hoqp_ab.sh).
-#ifdef HQ_INL_chol_floor
-#define HQ_ATTR_chol_floor always_inline
-#else
-#define HQ_ATTR_chol_floor noinline
-#endif
-#ifdef HQ_INL_chol_solve
-#define HQ_ATTR_chol_solve always_inline
-#else
-#define HQ_ATTR_chol_solve noinline
-#endif
-#ifdef HQ_INL_row_dot
-#define HQ_ATTR_row_dot always_inline
-#else
-#define HQ_ATTR_row_dot noinline
-#endif
-#ifdef HQ_INL_rt_dot
-#define HQ_ATTR_rt_dot always_inline
-#else
-#define HQ_ATTR_rt_dot noinline
-#endif
-#ifdef HQ_INL_hy_dot
-#define HQ_ATTR_hy_dot always_inline
-#else
-#define HQ_ATTR_hy_dot noinline
-#endif
-#ifdef HQ_INL_form_K
-#define HQ_ATTR_form_K always_inline
-#else
-#define HQ_ATTR_form_K noinline
-#endif
+// The per-iteration helpers (chol_floor, chol_solve, row_dot, rt_dot, hy_dot, form_K) are outlined: inlining any of
+// them moved the WBC launch by -0.3 to +0.5 % (round 3).
 namespace {
 
 struct HS {
@@ -279,7 +249,7 @@ __device__ __forceinline__ void sym_tiles(const ldouble* M, int ld, int rows, co
 // i's multiplier K_ik / d_k is lane-local.  Row updates stop at the last 16-wide block that holds live
 // columns.  The unit lower factor goes back to S.KL (lower part), dI[k] = 1 / d_k.
 template <int NP>
-__device__ __attribute__((HQ_ATTR_chol_floor)) void chol_floor(const HS& S_, int ls, int nd, int lane) {
+__device__ __attribute__((noinline)) void chol_floor(const HS& S_, int ls, int nd, int lane) {
     // local copy: members read through the reference (a flat pointer, which may alias LDS) would be reloaded
     // after every LDS store
     const HS S = S_;
@@ -348,8 +318,8 @@ __device__ __attribute__((HQ_ATTR_chol_floor)) void chol_floor(const HS& S_, int
 // substitution is one readlane broadcast and one fma, in blocks of 8 steps guarded by nd.  A lane's own entry
 // needs no select: its coefficients from its own step on are zero, so its accumulator stops at its solution.
 template <int NP>
-__device__ __attribute__((HQ_ATTR_chol_solve)) double chol_solve(const HS& S_, int ls, int nd, double rhs, ldouble* out,
-                                                       int lane) {
+__device__ __attribute__((noinline)) double chol_solve(const HS& S_, int ls, int nd, double rhs, ldouble* out,
+                                             int lane) {
     const HS S = S_;
     nd = uni(nd);
     ls = uni(ls);
@@ -398,7 +368,7 @@ __device__ __attribute__((HQ_ATTR_chol_solve)) double chol_solve(const HS& S_, i
 // t = R_r . vec (row r): 16-column blocks up to the level's live tiles, each block's 32 loads issued ahead of
 // its fmas (columns nd..16 nt - 1 of R and of vec are zero)
 template <int NP>
-__device__ __attribute__((HQ_ATTR_row_dot)) double row_dot(const HS& S_, int ls, int nd, int r, const ldouble* vec) {
+__device__ __attribute__((noinline)) double row_dot(const HS& S_, int ls, int nd, int r, const ldouble* vec) {
     const HS S = S_;
     ls = uni(ls);
     const int nt = nd_tiles(uni(nd));
@@ -419,7 +389,7 @@ __device__ __attribute__((HQ_ATTR_row_dot)) double row_dot(const HS& S_, int ls,
 }
 // (R' q)_j for lane j: 16-row blocks, each block's 32 loads issued ahead of its fmas; rows past nr are never
 // read (that LDS is not written at this level)
-__device__ __attribute__((HQ_ATTR_rt_dot)) double rt_dot(const HS& S_, int ls, int nr, const ldouble* q, int lane) {
+__device__ __attribute__((noinline)) double rt_dot(const HS& S_, int ls, int nr, const ldouble* q, int lane) {
     const HS S = S_;
     nr = uni(nr);
     ls = uni(ls);
@@ -451,8 +421,8 @@ __device__ __attribute__((HQ_ATTR_rt_dot)) double rt_dot(const HS& S_, int ls, i
 // every live 16-row block loaded in one batch (one global round trip); rows nd..16 nt - 1 of Hg and y are
 // zero, so the block-wide sum is exact
 template <int NP>
-__device__ __attribute__((HQ_ATTR_hy_dot)) double hy_dot(const HoqpDev& P_, const gdouble* Hg, const ldouble* y, int nd,
-                                                   int lane) {
+__device__ __attribute__((noinline)) double hy_dot(const HoqpDev& P_, const gdouble* Hg, const ldouble* y, int nd,
+                                             int lane) {
     const HoqpDev P = uniform(P_);
     const int nt = nd_tiles(uni(nd));
     double hv[NP];
@@ -711,8 +681,8 @@ __device__ __attribute__((noinline)) void level_setup(const HoqpDev& P_, const H
 }
 
 // K = Hy + R' diag(wh) R on the matrix cores (lower tiles covering nd) into S.KL.
-__device__ __attribute__((HQ_ATTR_form_K)) void form_K(const HoqpDev& P_, const HS& S_, int nr, int nd, const gdouble* Hg,
-                                                 int lane) {
+__device__ __attribute__((noinline)) void form_K(const HoqpDev& P_, const HS& S_, int nr, int nd, const gdouble* Hg,
+                                           int lane) {
     const HS S = S_;
     const HoqpDev P = uniform(P_);
     nr = uni(nr);
@@ -765,7 +735,7 @@ __device__ __attribute__((noinline)) void build_rows(const HoqpDev& P_, const HS
 // rows:  K_A = Hy + sum_violated R_r'R_r + rho R_A'R_A (an augmented-Lagrangian term: the same constrained
 // optimum, and K_A invertible where only the active rows bind), d0 = K_A^-1 (rhs - K_A y_i), y0 = y_i + d0,
 // T = K_A^-1 R_A' (one solve per active row), (R_A T) lambda = R_A y0 - h_A (LDL' with the same pivot floor),
-// y = y0 - T lambda.  The classification is repaired for up to XO_ROUNDS rounds -- the most negative multiplier
+// y = y0 - T lambda.  The classification is repaired for up to LMPC_HQ_XO_ROUNDS rounds -- the most negative multiplier
 // out, the most violated inactive frozen row in, own rows moved to the side they land on -- and the answer is
 // taken only if it then verifies: lambda >= 0, every row on its side, and the stationarity residual
 // Hy y + c + R'z within 1e-9 of the level's scale; otherwise the iterate is kept.  Returns the verdict
@@ -775,10 +745,7 @@ __device__ __attribute__((noinline)) void build_rows(const HoqpDev& P_, const HS
 // level-2 crossovers failed after the first pass (the level resumed the interior point and tried again) and 27
 // levels kept the iterate in the end; with 12, 10 and 7 (9 rounds: 10 kept, 16: 7).  Fewer resumed levels make the
 // 4096-chain launch 2 % faster (4.35 vs 4.44 ms); every golden level verifies either way.
-#ifndef LMPC_HQ_XO_ROUNDS  // -D: diagnostic A/B builds only
-#define LMPC_HQ_XO_ROUNDS 12
-#endif
-constexpr int XO_ROUNDS = LMPC_HQ_XO_ROUNDS;
+constexpr int LMPC_HQ_XO_ROUNDS = 12;
 #ifdef LMPC_HQ_ITDIAG  // diagnostic builds only: why the last crossover of a chain failed (bits 28-30 of the word)
 __device__ int lmpc_hq_xo_reason[65536];
 __device__ int lmpc_hq_nnls[65536];  // NNLS calls (low 6 bits) and successes (x 64)
@@ -787,16 +754,7 @@ __device__ int lmpc_hq_nnls[65536];  // NNLS calls (low 6 bits) and successes (x
 #define HQ_XO_FAIL(code) do {} while (0)
 #endif
 constexpr double HQ_HFLOOR = 1e-10;  // interior-point margin on exactly tight frozen rows (kernel, below)
-#ifndef LMPC_HQ_XO_TOL
-#define LMPC_HQ_XO_TOL 1e-9
-#endif
-constexpr double HQ_XO_TOL = LMPC_HQ_XO_TOL;  // first-pass interior-point stop ahead of the crossover (two passes)
-// Diagnostic A/B (tools/build): the first pass also stops after this many iterations (0 = no cap) and hands its
-// iterate to the crossover; a level whose crossover does not verify resumes as after a first-pass stop.
-#ifndef LMPC_HQ_XO_EARLY
-#define LMPC_HQ_XO_EARLY 0
-#endif
-constexpr int HQ_XO_EARLY = LMPC_HQ_XO_EARLY;
+constexpr double LMPC_HQ_XO_TOL = 1e-9;  // first-pass interior-point stop ahead of the crossover (two passes)
 // Multipliers of a degenerate active set (round 6).  Where the active frozen rows are linearly dependent (a foot at
 // the apex of its friction pyramid: four faces tight in three dimensions), the Schur complement R_A T' is singular,
 // its floored LDL' picks one multiplier vector of many and that one can have negative entries although a non-negative
@@ -805,9 +763,6 @@ constexpr int HQ_XO_EARLY = LMPC_HQ_XO_EARLY;
 // verification checks) by Lawson-Hanson NNLS on the active rows (normal equations of the passive set by chol_floor /
 // chol_solve; passive sets of at most na rows, at most 3 na + 3 outer steps).  Returns lambda in lane a (active row
 // S.rt[a]) and whether its residual is within tol.  Uses S.vb, S.KL, S.dI and (through chol_floor) S.dy.
-#ifndef LMPC_HQ_XO_NNLS
-#define LMPC_HQ_XO_NNLS 1
-#endif
 template <int NP>
 __device__ __attribute__((noinline)) double nnls_rows(const HS& S_, int ls, int na, int nd, double gr, double tol,
                                                       bool& ok, int lane) {
@@ -928,7 +883,7 @@ __device__ __attribute__((noinline)) bool crossover(const HoqpDev& P_, const HS&
         const int r = lane + 64 * k;
         tyi[k] = r < nr ? row_dot<NP>(S, ls, nd, r, S.y) : 0.0;
     }
-    for (int rd = 0; rd < XO_ROUNDS; ++rd) {
+    for (int rd = 0; rd < LMPC_HQ_XO_ROUNDS; ++rd) {
         // weights of K_A and the correction's right-hand side: rhs - K_A y_i = -c - Hy y_i + R' (w (bd - R y_i))
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
@@ -1018,7 +973,6 @@ __device__ __attribute__((noinline)) bool crossover(const HoqpDev& P_, const HS&
             }
             if (lane < np) S.dy[lane] = lane < nd ? y : 0.0;
             LMPC_SYNC();
-#if LMPC_HQ_XO_NNLS
             // dependent active rows with a negative multiplier: non-negative multipliers for the same point, if some
             // exist (nnls_rows); the point y is the one above either way
             // (only where the point meets every active row: dependent rows whose bounds disagree have no such point)
@@ -1044,7 +998,6 @@ __device__ __attribute__((noinline)) bool crossover(const HoqpDev& P_, const HS&
                 LMPC_SYNC();
                 if (ok) lam = ln;
             }
-#endif
         }
         // verification, and the repair of the classification
         double t[2];
@@ -1249,21 +1202,21 @@ __global__ void __launch_bounds__(64) lmpc_hoqp_kernel(const HoqpDev P, const do
         bool numstop = false;  // left on a non-finite Newton direction
         bool clean = false;    // stopped on the clean criterion (complementarity and residuals within tolerance)
         double mu_last = 0.0, res_last = 0.0;
-        // Two passes (round 3): with the crossover on, the interior point first stops at HQ_XO_TOL (or tol_mu, if
+        // Two passes (round 3): with the crossover on, the interior point first stops at LMPC_HQ_XO_TOL (or tol_mu, if
         // looser) and hands its iterate to the crossover; only a level whose crossover does not verify resumes the
         // interior point from that iterate down to tol_mu and tries the crossover again.  The verified answer is
         // the active-set optimum either way.  At 1e-9 every level of the committed WBC golden chains verifies
         // (4.83 -> 4.43 ms per 4096 WBC chains); at 1e-7 (4.00 ms) one of their 48 levels keeps its iterate
         // (1.6e-9 off), because the flat-direction components of the exact answers above it change
         // (tools/hoqp_xo_check.py, profiles/r03/hoqp_2pass/).
-        const bool two_pass = P.crossover && P.tol_mu < HQ_XO_TOL;
+        const bool two_pass = P.crossover && P.tol_mu < LMPC_HQ_XO_TOL;
         bool exact = false;
         int xo = 0;  // iteration word bits 16-17: 1 crossover tried, 2 verified and taken
 #ifdef LMPC_HQ_ITDIAG
         int it_p0 = 0;
 #endif
         for (int pass = two_pass ? 0 : 1; pass < 2; ++pass) {
-            const double tmu = pass == 0 ? HQ_XO_TOL : P.tol_mu;
+            const double tmu = pass == 0 ? LMPC_HQ_XO_TOL : P.tol_mu;
             for (;; ++it) {
                 // residuals: r_d = H x + c + C'z, r_p = C x + slack - d
                 double rp1[2], rpg[2], rdv[2];
@@ -1308,8 +1261,7 @@ __global__ void __launch_bounds__(64) lmpc_hoqp_kernel(const HoqpDev P, const do
                 // its tolerance while the dual residual stalls within 1e3 of its own, where the huge weights z/s
                 // of those rows leave the Newton directions no more accurate than the iterate already is
                 clean = mu <= tmu * scale && res <= P.tol_res * scale;
-                if (clean || (mu <= 1e-3 * tmu * scale && res <= 1e3 * P.tol_res * scale) || it >= P.max_iter ||
-                    (HQ_XO_EARLY > 0 && pass == 0 && it >= HQ_XO_EARLY))
+                if (clean || (mu <= 1e-3 * tmu * scale && res <= 1e3 * P.tol_res * scale) || it >= P.max_iter)
                     break;
                 // weights and K = Hy + R' diag(wh) R
                 double w1[2], wg[2], dl[2], is1[2], isg[2], idl[2];  // weights and the reciprocals both Newton

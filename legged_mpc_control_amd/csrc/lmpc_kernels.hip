@@ -229,20 +229,10 @@ __device__ __forceinline__ double n_eval(const NCoef& n, double ck, double sk, d
 
 // W: the calling kernel's waves-per-SIMD budget -- one copy per budget, so each copy is register-
 // allocated for its caller's occupancy (a shared callee would take the larger budget into both)
+// riccati_factor and riccati_solve are outlined.  Inlined at their one call site (to drop the call-saved register
+// traffic) the factor ran config 4 in 20.3 ms against 19.6, the solve in 26.8, both in 49.9.
 template <int W>
-// Diagnostic builds only (tools/build, -DLMPC_FACTOR_INLINE / -DLMPC_SOLVE_INLINE): the factor / solve inlined at
-// their one call site instead of outlined (A/B of the call-saved register traffic).
-#ifdef LMPC_FACTOR_INLINE
-#define LMPC_FACTOR_ATTR always_inline
-#else
-#define LMPC_FACTOR_ATTR noinline
-#endif
-#ifdef LMPC_SOLVE_INLINE
-#define LMPC_SOLVE_ATTR always_inline
-#else
-#define LMPC_SOLVE_ATTR noinline
-#endif
-__device__ __attribute__((LMPC_FACTOR_ATTR)) void riccati_factor(const Smem S, gdouble* __restrict__ gs, int H, const double dt,
+__device__ __attribute__((noinline)) void riccati_factor(const Smem S, gdouble* __restrict__ gs, int H, const double dt,
                                                          const int lane) {
     H = __builtin_amdgcn_readfirstlane(H);  // wave-uniform (arguments arrive in VGPRs): scalar loop control
     const int lc = lane & 15, lr = lane >> 4;  // accumulator layout: column lc, rows lr + 4i
@@ -503,7 +493,7 @@ __device__ __attribute__((LMPC_FACTOR_ATTR)) void riccati_factor(const Smem S, g
 // forward sweep (their L2 latency hides behind the serial recursion).
 // ---------------------------------------------------------------------------
 template <int NT12, int W>
-__device__ __attribute__((LMPC_SOLVE_ATTR)) void riccati_solve(const Smem S, const gdouble* __restrict__ gs, int H,
+__device__ __attribute__((noinline)) void riccati_solve(const Smem S, const gdouble* __restrict__ gs, int H,
                                                         const double dt, const int lane) {
     constexpr int NT6 = (NT12 + 1) / 2;
     H = __builtin_amdgcn_readfirstlane(H);  // wave-uniform (arguments arrive in VGPRs): scalar loop control
@@ -1279,12 +1269,8 @@ __global__ void __launch_bounds__(64, WPE) lmpc_qp_kernel(const DevParams prm, c
                         if (dz[t][i] < 0.0) dmax = fmin(dmax, -z[t][i] * __builtin_amdgcn_rcp(dz[t][i]));
                     }
                 }
-#if LMPC_SPLIT_STEP
                 const double alpha = fmin(1.0, LMPC_STEP_FRAC * wave_min(amax));
                 const double alpd = fmin(1.0, LMPC_STEP_FRAC * wave_min(dmax));
-#else
-                const double alpha = fmin(1.0, LMPC_STEP_FRAC * wave_min(fmin(amax, dmax))), alpd = alpha;
-#endif
 #pragma unroll
                 for (int t = 0; t < LS; ++t) {
                     if (!st[t]) continue;
@@ -1513,11 +1499,7 @@ hipError_t launch_qp(const DevParams& prm, const double* rec, const uint8_t* con
     // device has SIMDs (up to one QP per SIMD the lone-wave instance, free of spills, is faster); H <= 16
     // only: the LS = 2 state spills too much at 256 registers (measured at H = 20, 5 QPs per CU: 22 %
     // slower than 4 at one wave per SIMD).  Same arithmetic, so the choice never changes a result bit.
-#ifdef LMPC_AB_NO_W2  // diagnostic variant (tools/ab_bench.sh): the lone-wave instance only
-    const bool w2 = false;
-#else
     const bool w2 = !two && 5 * lds_bytes(prm.H, normals != nullptr) <= LMPC_CU_LDS_BYTES && batch > 4 * prm.cus;
-#endif
 #define LMPC_LAUNCH(LS_, T_, W_) \
     launch_variant<LS_, T_, W_>(prm, rec, contact, normals, batch, grf, status, iters, scratch, done, stream)
     if (normals) {

@@ -80,10 +80,6 @@ LMPC_LQ_INST(1, false, 2)
 LMPC_LQ_INST(2, false, 1)
 LMPC_LQ_INST(1, true, 1)
 LMPC_LQ_INST(1, true, 2)
-#ifdef LMPC_AB_W3  // diagnostic variant: three waves per SIMD (168 registers)
-LMPC_LQ_INST(1, false, 3)
-LMPC_LQ_INST(1, true, 3)
-#endif
 LMPC_LQ_INST(2, true, 1)
 LMPC_LQ_INST(2, false, 2)
 LMPC_LQ_INST(2, true, 2)
@@ -106,24 +102,18 @@ static void launch_lq_variant(const DevParams& prm, const double* rec, const uin
 // QPs on one SIMD while others idle).  At two leg-steps per lane (H > 16) the two-wave instance spills 276 B/lane:
 // where six or more QPs fit a CU's LDS (H <= 21) the waves it adds hide more than that costs -- config 3 (H = 20,
 // 8192 QPs) 3.667 -> 3.454 ms -- but at five per CU (H = 22..26) it is 8 % slower than the lone wave (round 6,
-// profiles/r06/ls2w2/).  At H = 30 four QPs fill the LDS.  Same arithmetic: the choice never changes a result bit.
+// profiles/r06/ls2w2/).  At H = 30 four QPs fill the LDS.  A three-waves-per-SIMD instance for H = 10 (without the
+// closed-loop rows, so that eleven QPs fit a CU) ran config 4 in 10.12 ms against 9.18 (profiles/r06/w3/ab.log) and
+// was removed.  Same arithmetic: the choice never changes a result bit.
 hipError_t launch_lq(const DevParams& prm, const double* rec, const uint8_t* contact, const double* normals, int batch,
                      double* grf, int32_t* status, int32_t* iters, const uint8_t* done, hipStream_t stream) {
     const bool two = 4 * prm.H > 64;
-#ifdef LMPC_AB_NO_W2  // diagnostic variant (tools/ab_bench.sh): the lone-wave instance only
-    const bool w2 = false;
-#else
     const bool w2 = (two ? 6 : 5) * lq_lds_bytes(prm.H) <= LMPC_CU_LDS_BYTES && batch > 4 * prm.cus;
-#endif
 #define LMPC_LQ_LAUNCH(LS_, T_, W_) \
     launch_lq_variant<LS_, T_, W_>(prm, rec, contact, normals, batch, grf, status, iters, done, stream)
     if (normals) {
         if (two) w2 ? LMPC_LQ_LAUNCH(2, true, 2) : LMPC_LQ_LAUNCH(2, true, 1);
-#ifdef LMPC_AB_W3
-        else w2 ? LMPC_LQ_LAUNCH(1, true, 3) : LMPC_LQ_LAUNCH(1, true, 1);
-#else
         else w2 ? LMPC_LQ_LAUNCH(1, true, 2) : LMPC_LQ_LAUNCH(1, true, 1);
-#endif
     } else {
         if (two) w2 ? LMPC_LQ_LAUNCH(2, false, 2) : LMPC_LQ_LAUNCH(2, false, 1);
         else w2 ? LMPC_LQ_LAUNCH(1, false, 2) : LMPC_LQ_LAUNCH(1, false, 1);

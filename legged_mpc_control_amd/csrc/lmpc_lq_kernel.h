@@ -82,14 +82,13 @@ constexpr int LQF_SINK = 332;  // 64: stores of lanes that hold no pivot row / n
 constexpr int LQF_EX = 396;    // 32: exchange buffer of the serial sweeps
 constexpr int LQF_CS = 428;    // 2H: cos / sin of the reference yaw per step
 constexpr int LQF_FIXED = 428;
-// At H <= LQ_KZ_MAXH (one leg-step per lane) the closed-loop rows KZ = K Z (6 x 12 per stage) are kept too, after the
+// At H <= LMPC_LQ_KZ_MAXH (one leg-step per lane) the closed-loop rows KZ = K Z (6 x 12 per stage) are kept too, after the
 // slots: the forward sweep is then one 12-term product per row (x' = A x + dv - KZ x - t, t = K za + rho in the rho
 // field) instead of w = Z x + za followed by K w; eight QPs per CU still fit at H = 10.
-#ifndef LMPC_LQ_KZ_MAXH  // diagnostic A/B: 0 = no closed-loop rows (a different forward-sweep formula, other bits)
-#define LMPC_LQ_KZ_MAXH 10
-#endif
-constexpr int LQ_KZ_MAXH = LMPC_LQ_KZ_MAXH;
-__host__ __device__ constexpr bool lq_kzs(int H) { return H <= LQ_KZ_MAXH; }
+// Without the rows (the other forward-sweep formula, other bits) config 4 ran 10.07 ms against 9.18
+// (profiles/r06/w3/ab.log).
+constexpr int LMPC_LQ_KZ_MAXH = 10;
+__host__ __device__ constexpr bool lq_kzs(int H) { return H <= LMPC_LQ_KZ_MAXH; }
 __host__ __device__ constexpr int lq_lds_doubles(int H) {
     return LQF_FIXED + 2 * H + LQ_SLOT * H + (lq_kzs(H) ? 72 * H : 0);
 }
@@ -119,42 +118,19 @@ __device__ __forceinline__ double lq_Ax(Ptr x, int r, double ck, double sk, doub
     return x[r];
 }
 
-// The factorisation sweep reads the lane index once per sweep (bit 0: for the stage body, bit 1: for the operand
-// fetch), so its lane-static offsets and masks are computed once per sweep instead of once per stage (478 -> 187
-// instructions per stage).  That fits 256 registers at two waves per SIMD only because every other pass takes its
-// own opaque copy of the lane index (no lane address lives across the sweep) and the reduced stage reads its U row
-// late (LMPC_LQ_LATE); config 4 10.8 -> 9.9 ms.  0 restores the per-stage maps (diagnostic).
-#ifndef LMPC_LQ_HOIST
-#define LMPC_LQ_HOIST 3
-#endif
-// the same choice for the two-wave instance at two leg-steps per lane (round 6: H = 17..26)
-#ifndef LMPC_LQ_HOIST_LS2W2
-#define LMPC_LQ_HOIST_LS2W2 3
-#endif
+// The factorisation sweep reads the lane index once per sweep, for the stage body and for the operand fetch, so its
+// lane-static offsets and masks are computed once per sweep instead of once per stage (478 -> 187 instructions per
+// stage).  That fits 256 registers at two waves per SIMD only because every other pass takes its own opaque copy of
+// the lane index (no lane address lives across the sweep) and the reduced stage reads its U row late (below); config 4
+// 10.8 -> 9.9 ms.  The two-wave instance at two leg-steps per lane (round 6: H = 17..21) hoists them
+// too and pays in spills.  Hoisting only one of the two map sets, or none, was slower in both instances (DESIGN.md,
+// "Experiments removed from the source").
 // At two waves per SIMD the reduced stage reads its U row after the pivot staging and stores Z_k after the solve
 // (shorter live ranges across the 6 x 6 factor; the lone-wave instances keep the early read, 2 % faster there -- the
-// same arithmetic either way, so every instance gives the same bits); 0 = the early read everywhere (diagnostic)
-// 1 fences the next stage's operand fetch off from the machine scheduler (one block between the stage's first
-// matrix-core chain and its leg-block work: round 4's choice under max-ilp).  Under iterative-ilp (round 5) the
-// scheduler places it better on its own: configs 3/4/5 -1.7/-0.3/-1.6 % without the fence
-// (profiles/r05/fused/ab_lq_fence_hoist.log), so 0 is the default; 1 is kept for A/B.
-#ifndef LMPC_LQ_FETCH_FENCE
-#define LMPC_LQ_FETCH_FENCE 0
-#endif
-// 1 loads a serial-sweep stage's operands one stage ahead in the lone-wave instance (round 4).  Under iterative-ilp
-// (round 5) loading them in the stage is faster -- the second operand set's registers cost more than the load
-// latency they hid: config 2 --dense off -3 %, configs 3/5 -2 % (profiles/r05/fused/ab_lq_late_prefetch.log).
-// reduced-input polish stages also at two leg-steps per lane (diagnostic A/B; see LQ_RP in the kernel)
-#ifndef LMPC_LQ_RP2
-#define LMPC_LQ_RP2 0
-#endif
-#ifndef LMPC_LQ_PF
-#define LMPC_LQ_PF 0
-#endif
-#ifndef LMPC_LQ_LATE
-#define LMPC_LQ_LATE 1
-#endif
-constexpr bool LQ_LATE_ON = LMPC_LQ_LATE != 0;
+// same arithmetic either way, so every instance gives the same bits).
+// The machine scheduler (iterative-ilp) places the next stage's operand fetch on its own, and a serial-sweep stage
+// loads its operands in the stage: round 4's fetch fence and its one-stage-ahead prefetch with a second operand set
+// both lost under that scheduler (profiles/r05/fused/ab_lq_fence_hoist.log, ab_lq_late_prefetch.log).
 
 __device__ __forceinline__ int lq_opaque(int v) {
     asm volatile("" : "+v"(v));
@@ -162,12 +138,9 @@ __device__ __forceinline__ int lq_opaque(int v) {
 }
 // The lane index for the lane-static operand maps of a phase: opaque at two waves per SIMD (recomputed where used:
 // 256 registers cannot hold them across the solve), plain in the lone-wave instance (512 registers: computed once).
-#ifndef LMPC_LQ_OPAQUE_W1
-#define LMPC_LQ_OPAQUE_W1 0
-#endif
 template <int WPE>
 __device__ __forceinline__ int lq_lane(int lane) {
-    return (WPE == 1 && !LMPC_LQ_OPAQUE_W1) ? lane : lq_opaque(lane);
+    return WPE == 1 ? lane : lq_opaque(lane);
 }
 
 // The same products branch-free for a runtime row r: (A x)[r] = x[r] + dt (a1 x[c1] + a2 x[c2]) and
@@ -256,15 +229,11 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
     const double* rin = rec + (size_t)qp * RL;
     const double* xr = rin + 33;  // x_ref (global, L2-resident after its first use)
     const double mu = prm.mu, fzmax = prm.fmax, dt = prm.dt;
-    // the serial sweeps can load a stage's operands one stage ahead in the lone-wave instance (LMPC_LQ_PF, off by
-    // default since round 5); at two waves per SIMD the second set of registers would spill
-    constexpr bool LQ_PF = LMPC_LQ_PF && WPE == 1;
-    constexpr bool LQ_LATE = LQ_LATE_ON && WPE == 2;
-    constexpr int LQ_HOIST = (LS == 2 && WPE == 2) ? LMPC_LQ_HOIST_LS2W2 : LMPC_LQ_HOIST;
+    constexpr bool LQ_LATE = WPE == 2;  // the reduced stage's late U-row read (above)
     // reduced-input polish stages (well-conditioned W_k) at one leg-step per lane: measured -1.2 % on config 4 (stages
     // with three or four stance legs), +2.5 % on config 2 with the dense path off (a trot's full polish stage has only
     // two pivot blocks); both instances alike, as kzs above; at two leg-steps per lane the leg-step work is not repaid
-    constexpr bool LQ_RP = LS == 1 || LMPC_LQ_RP2;
+    constexpr bool LQ_RP = LS == 1;
     LQ_STAMP_DECL
 
     // ---- prologue: record, terrain frames, I_w^-1, G0, yaw cos / sin ----------------------------------------
@@ -706,9 +675,7 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
                 {
                     const int lnb = lq_lane<WPE>(lane), r = lnb < 12 ? lnb : 0;
                     const int m = lnb < 6 ? lnb : 0;
-                    // a stage's operands are loaded while the stage before it runs: an LDS load cannot move above
-                    // the fence that orders the exchange buffer, so loaded in the stage itself they would wait a
-                    // round trip on the serial path
+                    // a stage's operands are loaded at the top of the stage, ahead of the exchange-buffer fence
                     struct BwOps {
                         double v, rho, q, ck, sk, kr[6], zc[6];
                     };
@@ -724,15 +691,14 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
 #pragma unroll
                         for (int mm = 0; mm < 6; ++mm) o.zc[mm] = sl[LQ_Z + mm * 13 + r];
                     };
-                    BwOps cur, nxt;
+                    BwOps cur;
                     load(H - 1, cur);
                     double p = lnb < 12 ? slots[(H - 1) * LQ_SLOT + LQ_X + r] : 0.0;
                     for (int k = H - 1; k >= 0; --k) {
-                        if (!LQ_PF && k < H - 1) load(k, cur);
+                        if (k < H - 1) load(k, cur);
                         const double y = p + cur.v;
                         if (lnb < 12) ex[r] = y;
                         if (lnb >= 6 && lnb < 12) slots[k * LQ_SLOT + LQ_Z + (lnb - 6) * 13 + 12] = y;
-                        if (LQ_PF && k > 0) load(k - 1, nxt);
                         LMPC_SYNC();
                         if (k == 0) break;
                         // t_m = sum_n K[m][n] y[6+n] + rho_m, lanes 0-5
@@ -743,16 +709,15 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
 #pragma unroll
                         for (int mm = 0; mm < 6; ++mm) pn = fma(-cur.zc[mm], readlane_f64(tv, mm), pn);
                         p = pn;
-                        if (LQ_PF) cur = nxt;
                         LMPC_SYNC();
                     }
                 }
                 LQ_STAMP(2);  // corrector backward
             } else {
                 // ======== factorisation with the fused backward pass (stage k = H-1 .. 0) ========
-                // The lane-static operand maps are recomputed in every stage from an opaque copy of the lane index
-                // (integer work off the critical path): held across the loop -- or hoisted out of the solve loop by
-                // loop-invariant code motion -- they would stay live through every other phase and push the kernel's
+                // The lane-static operand maps come from one opaque copy of the lane index per sweep (sfl below): they
+                // stay in registers across the stages of this sweep and die with it -- hoisted out of the solve loop by
+                // loop-invariant code motion they would stay live through every other phase and push the kernel's
                 // long-lived state past the 256 registers of two waves per SIMD.
                 // interior point: reduced inputs -- B^ rows 6-11 = [U | 0 | dv'], unit input Hessian, X = L^-1 [0 | U' | 0],
                 // two 3x3 pivot blocks whatever the stage's leg count; polish: Bt, Rr_j, rr as staged by the legs
@@ -811,11 +776,12 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
                 auto sweep = [&](auto red_tag) {
                     constexpr bool red = decltype(red_tag)::value;
                     constexpr int UF = red ? LQ_Z : LQ_K;  // where U_k is (the polish stages Bt in the Z field)
-                    const int sfl = lq_lane<WPE>(lane);  // one lane read for the whole sweep (its offsets stay in registers)
+                    // one lane read for the whole sweep (its offsets stay in registers)
+                    const int sfl = lq_lane<WPE>(lane);
                     double bg[2], xg[3], qn[3], ckn, skn;
                     bool sfn;
                     auto fetch = [&](int k) {
-                        const int fl = (LQ_HOIST & 2) ? sfl : lq_lane<WPE>(lane), lc = fl & 15, lr = fl >> 4;
+                        const int lc = sfl & 15, lr = sfl >> 4;
                         const ldouble* sl = slots + k * LQ_SLOT;
                         ckn = cs[2 * k];
                         skn = cs[2 * k + 1];
@@ -856,7 +822,7 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
                     };
                     fetch(H - 1);
                     for (int k = H - 1; k >= 0; --k) {
-                        const int fl = (LQ_HOIST & 1) ? sfl : lq_lane<WPE>(lane), lc = fl & 15, lr = fl >> 4;
+                        const int fl = sfl, lc = fl & 15, lr = fl >> 4;
                         ldouble* sl = slots + k * LQ_SLOT;
                         const double ck = ckn, sk = skn;
                         const bool sr = red || sfn;
@@ -883,13 +849,7 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
                         G = MFMA64(bh[0], C[1], G);
                         G = MFMA64(bh[1], C[2], G);
                         // next stage's operands, issued while the matrix cores work through the chain above
-#if LMPC_LQ_FETCH_FENCE
-                        __builtin_amdgcn_sched_barrier(0);
-#endif
                         fetch(k > 0 ? k - 1 : 0);
-#if LMPC_LQ_FETCH_FENCE
-                        __builtin_amdgcn_sched_barrier(0);
-#endif
                         // reduced inputs: this lane's U row (c = lc - 6, for its X columns), read before Z_k overwrites U_k
                         double ur[6];
                         auto read_ur = [&]() {
@@ -1158,7 +1118,7 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
                         o.ck = cs[2 * ky];
                         o.sk = cs[2 * ky + 1];
                     };
-                    KzOps cur, nxt;
+                    KzOps cur;
                     load(0, cur);
                     if (lane < 12) ex[16 + lane] = hdr[lane];  // x0
                     LMPC_SYNC();
@@ -1167,8 +1127,7 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
                         const int a = ln < 24 ? (ln >> 2) : 0, part = ln & 3;
                         const int r = ln < 6 ? ln : 0;
                         const ldouble* x = ex + 16;
-                        if (!LQ_PF && k > 0) load(k, cur);
-                        if (LQ_PF && k + 1 < H) load(k + 1, nxt);
+                        if (k > 0) load(k, cur);
                         double w = cur.kz[0] * x[3 * part];
                         w = fma(cur.kz[1], x[3 * part + 1], w);
                         w = fma(cur.kz[2], x[3 * part + 2], w);
@@ -1176,7 +1135,6 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
                         const double xv = x[6 + a] + cur.c;
                         w = quad_sum(w);
                         const double xb = xv - w;
-                        if (LQ_PF) cur = nxt;
                         LMPC_SYNC();
                         if (ln < 6) {
                             ex[16 + r] = xa;
@@ -1192,8 +1150,7 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
                     struct FwOps {
                         double kr[6], base, za, z[3], ck, sk;
                     };
-                    // lane roles from an opaque lane index (addresses computed per stage, never hoisted at 256 registers);
-                    // a stage's operands are loaded while the stage before it runs (see the corrector's backward sweep)
+                    // lane roles from an opaque lane index (addresses computed per stage, never hoisted at 256 registers)
                     auto load = [&](int k, FwOps& o) {
                         const int ln = lq_lane<WPE>(lane);
                         const int m = ln < 24 ? (ln >> 2) : 0, part = ln & 3;  // w: lanes 4m..4m+3, 3 terms each
@@ -1214,7 +1171,7 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
                         o.ck = cs[2 * ky];
                         o.sk = cs[2 * ky + 1];
                     };
-                    FwOps cur, nxt;
+                    FwOps cur;
                     load(0, cur);
                     if (lane < 12) ex[16 + lane] = hdr[lane];  // x0
                     LMPC_SYNC();
@@ -1223,8 +1180,7 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
                         const int part = ln & 3;
                         const int r = ln < 12 ? ln : 0;
                         const ldouble* x = ex + 16;
-                        if (!LQ_PF && k > 0) load(k, cur);
-                        if (LQ_PF && k + 1 < H) load(k + 1, nxt);
+                        if (k > 0) load(k, cur);
                         double w = cur.z[0] * x[3 * part];
                         w = fma(cur.z[1], x[3 * part + 1], w);
                         w = fma(cur.z[2], x[3 * part + 2], w);
@@ -1247,7 +1203,6 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
                             k1 = fma(-cur.kr[mm + 3], wb[mm + 3], k1);
                         }
                         const double xn = xa + (r >= 6 ? k0 + k1 : 0.0);
-                        if (LQ_PF) cur = nxt;
                         LMPC_SYNC();
                         if (ln < 12) {
                             ex[16 + r] = xn;
@@ -1381,12 +1336,8 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
                         if (dz[t][i] < 0.0) dmax = fmin(dmax, -z[t][i] * __builtin_amdgcn_rcp(dz[t][i]));
                     }
                 }
-#if LMPC_SPLIT_STEP
                 const double alpha = fmin(1.0, LMPC_STEP_FRAC * wave_min(amax));
                 const double alpd = fmin(1.0, LMPC_STEP_FRAC * wave_min(dmax));
-#else
-                const double alpha = fmin(1.0, LMPC_STEP_FRAC * wave_min(fmin(amax, dmax))), alpd = alpha;
-#endif
 #pragma unroll
                 for (int t = 0; t < LS; ++t) {
                     if (!st[t]) continue;

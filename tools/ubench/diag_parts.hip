@@ -230,14 +230,6 @@ static __device__ __attribute__((noinline)) DiagInv diag_inverse_lag(ldouble* sc
         const double p20 = sT[so(2) + o], p21 = sT[so(2) + o + 1], p22 = sT[so(2) + o + 2];
         const double t0 = sT[so(0) + c], t1 = sT[so(1) + c], t2 = sT[so(2) + c];
         Piv f;
-#if LMPC_DIAG_SEQ_RSQ
-        f.i00 = rsq_nr(p00);
-        f.l10 = p10 * f.i00;
-        f.l20 = p20 * f.i00;
-        f.i11 = rsq_nr(fma(-f.l10, f.l10, p11));
-        f.l21 = fma(-f.l20, f.l10, p21) * f.i11;
-        f.i22 = rsq_nr(fma(-f.l21, f.l21, fma(-f.l20, f.l20, p22)));
-#else
         const double m11 = fma(p00, p11, -p10 * p10);
         const double c00 = fma(p11, p22, -p21 * p21), c01 = fma(p10, p22, -p21 * p20), c02 = fma(p10, p21, -p11 * p20);
         const double det = fma(p00, c00, fma(-p10, c01, p20 * c02));
@@ -248,7 +240,6 @@ static __device__ __attribute__((noinline)) DiagInv diag_inverse_lag(ldouble* sc
         f.i11 = (p00 * f.i00) * r1;
         f.l21 = fma(-f.l20, f.l10, p21) * f.i11;
         f.i22 = (m11 * r1) * r2;
-#endif
         const double x0 = t0 * f.i00;
         const double x1 = fma(-f.l10, x0, t1) * f.i11;
         const double x2 = fma(-f.l21, x1, fma(-f.l20, x0, t2)) * f.i22;

@@ -56,6 +56,12 @@ MULTI_SYMBOLS = (
 )
 MULTI_ABI_VERSION = 1
 LMPC_ERR_COMM = -6
+# include/lmpc/lmpc_rollout.h: the device-resident closed-loop rollout
+ROLLOUT_SYMBOLS = (
+    "lmpc_rollout_abi_version", "lmpc_robot_size", "lmpc_rollout_cfg_go1", "lmpc_robot_init", "lmpc_robot_plant_step",
+    "lmpc_robot_advance", "lmpc_shift_active_set_device", "lmpc_solve_commands_warm_device", "lmpc_rollout_device",
+)
+ROLLOUT_ABI_VERSION = 1
 
 
 class LmpcParams(ctypes.Structure):
@@ -124,6 +130,36 @@ class LmpcCommand(ctypes.Structure):
 
 
 COMMAND_BYTES = ctypes.sizeof(LmpcCommand)  # 408
+
+
+class LmpcRolloutCfg(ctypes.Structure):
+    _fields_ = [
+        ("default_feet", ctypes.c_double * 12),
+        ("swing_clearance", ctypes.c_double),
+        ("foot_delta_limit", ctypes.c_double * 2),
+        ("ground_z", ctypes.c_double),
+    ]
+
+
+class LmpcRobot(ctypes.Structure):
+    """Everything one robot carries between the ticks of a rollout (lmpc_robot)."""
+    _fields_ = [
+        ("cmd", LmpcCommand),
+        ("foot_pos_world", ctypes.c_double * 12),
+        ("swing_start_world", ctypes.c_double * 12),
+        ("fsm_start", ctypes.c_double * 4),
+        ("fsm_index", ctypes.c_int32 * 4),
+        ("tick", ctypes.c_int32),
+    ]
+
+
+ROBOT_BYTES = ctypes.sizeof(LmpcRobot)  # 656
+
+
+class LmpcRolloutLog(ctypes.Structure):
+    """Device pointers, each [ticks][batch]... or NULL (lmpc_rollout_log)."""
+    _fields_ = [("cmd", ctypes.c_void_p), ("u0", ctypes.c_void_p), ("x", ctypes.c_void_p),
+                ("status", ctypes.c_void_p), ("iters", ctypes.c_void_p)]
 
 
 class LmpcLegKin(ctypes.Structure):
@@ -296,6 +332,27 @@ def lib():
         L.lmpc_wbc_tasks.restype = ctypes.c_int
         L.lmpc_wbc_tasks_device.argtypes = [vp, ctypes.c_int, vp, vp]
         L.lmpc_wbc_tasks_device.restype = ctypes.c_int
+        rcp, rbp = ctypes.POINTER(LmpcRolloutCfg), ctypes.POINTER(LmpcRobot)
+        L.lmpc_rollout_abi_version.restype = ctypes.c_int
+        L.lmpc_robot_size.restype = ctypes.c_int
+        L.lmpc_rollout_cfg_go1.argtypes = [rcp]
+        L.lmpc_rollout_cfg_go1.restype = None
+        L.lmpc_robot_init.argtypes = [rcp, dp, dp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_double, rbp]
+        L.lmpc_robot_init.restype = ctypes.c_int
+        L.lmpc_robot_plant_step.argtypes = [pp, rbp, dp]
+        L.lmpc_robot_plant_step.restype = ctypes.c_int
+        L.lmpc_robot_advance.argtypes = [pp, rcp, rbp, dp, dp]
+        L.lmpc_robot_advance.restype = ctypes.c_int
+        L.lmpc_shift_active_set_device.argtypes = [vp, vp, ctypes.c_int, vp, vp]
+        L.lmpc_shift_active_set_device.restype = ctypes.c_int
+        L.lmpc_solve_commands_warm_device.argtypes = [vp, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp]
+        L.lmpc_solve_commands_warm_device.restype = ctypes.c_int
+        L.lmpc_rollout_device.argtypes = [vp, rcp, vp, vp, ctypes.c_int, ctypes.c_int,
+                                          ctypes.POINTER(LmpcRolloutLog), vp]
+        L.lmpc_rollout_device.restype = ctypes.c_int
+        if L.lmpc_rollout_abi_version() != ROLLOUT_ABI_VERSION or L.lmpc_robot_size() != ROBOT_BYTES:
+            raise NativeLibraryError(f"{path}: lmpc_rollout.h ABI {L.lmpc_rollout_abi_version()} / lmpc_robot of "
+                                     f"{L.lmpc_robot_size()} B, this binding is ABI {ROLLOUT_ABI_VERSION} / {ROBOT_BYTES} B")
         # exactly this ABI, diagnostic builds (LMPC_LIB) included: the command and options structs above are ABI-7
         # layouts, and an older library would read their fields at the wrong offsets without an error
         if L.lmpc_abi_version() != ABI_VERSION:

@@ -12,6 +12,8 @@
 #include <new>
 
 #include "lmpc/lmpc.h"
+#include "lmpc/lmpc_rollout.h"
+#include "lmpc_common.h"
 #include "lmpc_device.h"
 
 namespace lmpc {
@@ -34,6 +36,10 @@ hipError_t launch_normals(uint64_t seed, int64_t first, int count, double theta_
                           hipStream_t stream);
 hipError_t launch_torque(const lmpc_leg_kin& kin, const double* rec, const double* joint_pos, const double* grf,
                          int batch, int H, double* tau, hipStream_t stream);
+hipError_t launch_advance(const lmpc_common::PlantParams& pp, const lmpc_rollout_cfg& cfg, lmpc_robot* robots,
+                          int batch, const double* grf, int H, int book, lmpc_command* cmd_out, double* log_u0,
+                          double* log_x, double* rec, uint8_t* contact, hipStream_t stream);
+hipError_t launch_shift(const uint8_t* act, int batch, int H, uint8_t* shifted, hipStream_t stream);
 }
 
 struct lmpc_ctx {
@@ -57,6 +63,11 @@ struct lmpc_ctx {
     double* d_crec = nullptr;     // records expanded from commands (lmpc_solve_commands_device), grown on demand
     uint8_t* d_ccon = nullptr;
     size_t cmd_qps = 0;
+    // the rollout's own buffers (lmpc_rollout_device), grown on demand like d_crec: the solves' forces (u_0 is each
+    // QP's first 12) and the shifted active set
+    double* d_rgrf = nullptr;
+    uint8_t* d_ract = nullptr;
+    size_t roll_qps = 0;
     // Ordering of the context's own buffers (d_scratch, d_done, the staging blocks, d_crec/d_ccon) across
     // streams: a launch that uses them notes its stream (ctx_leave); the next such launch on another stream
     // records `ev` on the noted stream then and waits on it (ctx_enter); a host-pointer call, lmpc_sync and
@@ -191,6 +202,11 @@ void free_bufs(lmpc_ctx* c) {
     c->d_crec = nullptr;
     c->d_ccon = nullptr;
     c->cmd_qps = 0;
+    (void)hipFree(c->d_rgrf);
+    (void)hipFree(c->d_ract);
+    c->d_rgrf = nullptr;
+    c->d_ract = nullptr;
+    c->roll_qps = 0;
     c->d_in = c->d_out = c->h_in = c->h_out = nullptr;
 }
 
@@ -226,6 +242,39 @@ int ensure_ws(lmpc_ctx* c, int batch, bool scratch) {
         }
         c->scratch_qps = (size_t)batch;
     }
+    return LMPC_OK;
+}
+
+// The record buffers commands are expanded into (lmpc_solve_commands_device and its warm and rollout forms); the
+// caller has set the context's device.
+int ensure_cmd(lmpc_ctx* c, int batch) {
+    if ((size_t)batch <= c->cmd_qps) return LMPC_OK;
+    (void)hipDeviceSynchronize();  // the old buffers may still be read by queued work
+    (void)hipFree(c->d_crec);
+    (void)hipFree(c->d_ccon);
+    c->d_crec = nullptr;
+    c->d_ccon = nullptr;
+    c->cmd_qps = 0;
+    if (hipMalloc(&c->d_crec, (size_t)batch * lmpc_record_len(c->H) * sizeof(double)) != hipSuccess ||
+        hipMalloc(&c->d_ccon, (size_t)batch * 4 * c->H) != hipSuccess)
+        return LMPC_ERR_ALLOC;
+    c->cmd_qps = (size_t)batch;
+    return LMPC_OK;
+}
+
+// The rollout's buffers for `batch` robots.
+int ensure_roll(lmpc_ctx* c, int batch) {
+    if ((size_t)batch <= c->roll_qps) return LMPC_OK;
+    (void)hipDeviceSynchronize();
+    (void)hipFree(c->d_rgrf);
+    (void)hipFree(c->d_ract);
+    c->d_rgrf = nullptr;
+    c->d_ract = nullptr;
+    c->roll_qps = 0;
+    if (hipMalloc(&c->d_rgrf, (size_t)batch * 12 * c->H * sizeof(double)) != hipSuccess ||
+        hipMalloc(&c->d_ract, (size_t)batch * 4 * c->H) != hipSuccess)
+        return LMPC_ERR_ALLOC;
+    c->roll_qps = (size_t)batch;
     return LMPC_OK;
 }
 
@@ -542,18 +591,7 @@ int lmpc_solve_commands_device(lmpc_ctx* c, const lmpc_command* d_cmd, const dou
     if (!c || batch < 0 || (batch > 0 && (!d_cmd || !d_grf))) return LMPC_ERR_ARG;
     if (batch == 0) return LMPC_OK;
     LMPC_DEVICE_ENTRY(c, s);
-    if ((size_t)batch > c->cmd_qps) {
-        (void)hipDeviceSynchronize();  // the old buffers may still be read by queued work
-        (void)hipFree(c->d_crec);
-        (void)hipFree(c->d_ccon);
-        c->d_crec = nullptr;
-        c->d_ccon = nullptr;
-        c->cmd_qps = 0;
-        if (hipMalloc(&c->d_crec, (size_t)batch * lmpc_record_len(c->H) * sizeof(double)) != hipSuccess ||
-            hipMalloc(&c->d_ccon, (size_t)batch * 4 * c->H) != hipSuccess)
-            return LMPC_ERR_ALLOC;
-        c->cmd_qps = (size_t)batch;
-    }
+    if (ensure_cmd(c, batch) != LMPC_OK) return LMPC_ERR_ALLOC;
     // the expansion overwrites the context's record buffers: order it behind the previous solve that read them
     hipError_t e = ctx_enter(c, s);
     if (e == hipSuccess) e = lmpc::launch_records(d_cmd, batch, c->H, c->prm.dt, c->d_crec, c->d_ccon, s);
@@ -584,6 +622,91 @@ int lmpc_grf_to_torque_device(lmpc_ctx* c, const lmpc_leg_kin* k, const double* 
     if (batch == 0) return LMPC_OK;
     LMPC_DEVICE_ENTRY(c, s);
     return launch_rc(lmpc::launch_torque(*k, d_rec, d_joint_pos, d_grf, batch, c->H, d_tau, s));
+}
+
+// ---- include/lmpc/lmpc_rollout.h: the device entry points -----------------
+
+int lmpc_shift_active_set_device(lmpc_ctx* c, const uint8_t* d_act, int batch, uint8_t* d_shifted, void* stream) {
+    if (!c || batch < 0 || (batch > 0 && (!d_act || !d_shifted || d_act == d_shifted))) return LMPC_ERR_ARG;
+    if (batch == 0) return LMPC_OK;
+    LMPC_DEVICE_ENTRY(c, s);
+    return launch_rc(lmpc::launch_shift(d_act, batch, c->H, d_shifted, s));
+}
+
+// Every QP of the (already expanded) batch on the scratch Riccati kernel from act_in, as solve_host routes a warm call.
+static int solve_warm_device(lmpc_ctx* c, const double* d_rec, const uint8_t* d_con, const double* d_normals, int batch,
+                             const uint8_t* d_act_in, uint8_t* d_act_out, double* d_grf, int32_t* d_status,
+                             int32_t* d_iters, hipStream_t s) {
+    lmpc::DevParams prm = c->prm;
+    prm.dense = 0;  // the dense kernels are not warm-started
+    prm.warm_act = d_act_in;
+    prm.act_out = d_act_out;
+    const int rc = ensure_ws(c, batch, true);
+    if (rc != LMPC_OK) return rc;
+    hipError_t e = ctx_enter(c, s);
+    if (e == hipSuccess)
+        e = lmpc::launch_qp(prm, d_rec, d_con, d_normals, batch, d_grf, d_status, d_iters, c->d_scratch, nullptr, s);
+    if (e == hipSuccess) e = ctx_leave(c, s);
+    return launch_rc(e);
+}
+
+int lmpc_solve_commands_warm_device(lmpc_ctx* c, const lmpc_command* d_cmd, const double* d_normals, int batch,
+                                    const uint8_t* d_act_in, uint8_t* d_act_out, double* d_grf, int32_t* d_status,
+                                    int32_t* d_iters, void* stream) {
+    if (!c || batch < 0 || (batch > 0 && (!d_cmd || !d_grf || (d_act_in && d_act_in == d_act_out)))) return LMPC_ERR_ARG;
+    if (batch == 0) return LMPC_OK;
+    LMPC_DEVICE_ENTRY(c, s);
+    if (ensure_cmd(c, batch) != LMPC_OK) return LMPC_ERR_ALLOC;
+    hipError_t e = ctx_enter(c, s);
+    if (e == hipSuccess) e = lmpc::launch_records(d_cmd, batch, c->H, c->prm.dt, c->d_crec, c->d_ccon, s);
+    if (e != hipSuccess) return launch_rc(e);
+    return solve_warm_device(c, c->d_crec, c->d_ccon, d_normals, batch, d_act_in, d_act_out, d_grf, d_status, d_iters, s);
+}
+
+int lmpc_rollout_device(lmpc_ctx* c, const lmpc_rollout_cfg* cfg, lmpc_robot* d_robots, uint8_t* d_act, int batch,
+                        int ticks, const lmpc_rollout_log* log, void* stream) {
+    if (!c || !cfg || !d_robots || batch < 0 || ticks < 0) return LMPC_ERR_ARG;
+    LMPC_DEVICE_ENTRY(c, s);
+    if (batch == 0 || ticks == 0) return LMPC_OK;
+    // every buffer before the first launch: growing one synchronises the device
+    if (ensure_cmd(c, batch) != LMPC_OK || ensure_roll(c, batch) != LMPC_OK) return LMPC_ERR_ALLOC;
+    {
+        const int rc = ensure_ws(c, batch, d_act != nullptr || uses_scratch(c, c->prm));
+        if (rc != LMPC_OK) return rc;
+    }
+    lmpc_common::PlantParams pp;
+    pp.mass = c->prm.mass;
+    for (int i = 0; i < 9; ++i) pp.Ib[i] = c->prm.Ib[i];
+    pp.grav = c->prm.grav;
+    pp.dt = c->prm.dt;
+    static const lmpc_rollout_log no_log = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    const lmpc_rollout_log& lg = log ? *log : no_log;
+    const size_t B = (size_t)batch;
+    // the rollout's buffers are the context's: order the first launch behind whatever used them last
+    hipError_t e = ctx_enter(c, s);
+    if (e != hipSuccess) return launch_rc(e);
+    for (int t = 0; t <= ticks; ++t) {
+        const bool last = t == ticks;
+        // the advance launch also expands tick t's commands into the context's record buffers
+        e = lmpc::launch_advance(pp, *cfg, d_robots, batch, t > 0 ? c->d_rgrf : nullptr, c->H, last ? 0 : 1,
+                                 !last && lg.cmd ? lg.cmd + (size_t)t * B : nullptr,
+                                 t > 0 && lg.u0 ? lg.u0 + (size_t)(t - 1) * B * 12 : nullptr,
+                                 t > 0 && lg.x ? lg.x + (size_t)(t - 1) * B * 12 : nullptr, c->d_crec, c->d_ccon, s);
+        if (e != hipSuccess || last) break;
+        int32_t* st = lg.status ? lg.status + (size_t)t * B : nullptr;
+        int32_t* it = lg.iters ? lg.iters + (size_t)t * B : nullptr;
+        int rc;
+        if (d_act) {
+            e = lmpc::launch_shift(d_act, batch, c->H, c->d_ract, s);
+            if (e != hipSuccess) break;
+            rc = solve_warm_device(c, c->d_crec, c->d_ccon, nullptr, batch, c->d_ract, d_act, c->d_rgrf, st, it, s);
+        } else {
+            rc = lmpc_solve_batch_device_ex(c, c->d_crec, c->d_ccon, nullptr, batch, c->d_rgrf, st, it, s);
+        }
+        if (rc != LMPC_OK) return rc;
+    }
+    if (e == hipSuccess) e = ctx_leave(c, s);
+    return launch_rc(e);
 }
 #undef LMPC_DEVICE_ENTRY
 

@@ -5,6 +5,8 @@
 //   bound schedule                 ConvexQPSolver.cpp:329-346
 //   reference trajectory / x0      ConvexQPSolver.cpp:256-276
 //   synthetic commands             SURVEY.md 8d (Philox4x32-10 keyed by (seed, global index))
+//   the closed-loop tick           lmpc_rollout.h: plant step, Raibert foothold, leg FSM update, swing Bezier
+//                                  (compiled for gfx950 in lmpc_rollout.hip)
 //
 // Floating-point contraction is switched off in every function of this header (LMPC_NO_FMA) so the host (x86-64, no FMA) and the
 // device (FMA-capable) evaluate every non-transcendental expression identically: a command expands
@@ -16,6 +18,7 @@
 #include <cstdint>
 
 #include "lmpc/lmpc.h"
+#include "lmpc/lmpc_rollout.h"
 
 #if defined(__HIPCC__)
 #define LMPC_HD __host__ __device__
@@ -26,6 +29,7 @@
 #define LMPC_NO_FMA _Pragma("clang fp contract(off)")
 
 static_assert(sizeof(lmpc_command) == 408, "lmpc_command layout (mirrored by _native.LmpcCommand)");
+static_assert(sizeof(lmpc_robot) == 656, "lmpc_robot layout (mirrored by _native.LmpcRobot)");
 
 namespace lmpc_common {
 
@@ -288,6 +292,164 @@ LMPC_HD inline void leg_torque(const double rf[5], const double ro[3], const dou
     for (int r = 0; r < 3; ++r) fr[r] = rot[r] * f[0] + rot[3 + r] * f[1] + rot[6 + r] * f[2];
     foot_jacobian(rf, ro, q, J);
     for (int c = 0; c < 3; ++c) tau[c] = -(J[c] * fr[0] + J[3 + c] * fr[1] + J[6 + c] * fr[2]);
+}
+
+// ---- the closed-loop tick (include/lmpc/lmpc_rollout.h) --------------------
+// What the plant step reads of lmpc_params (host) / DevParams (device).
+struct PlantParams {
+    double mass;
+    double Ib[9];
+    double grav;
+    double dt;
+};
+
+// percent_in_state (LeggedContactFSM.cpp:269-278)
+LMPC_HD inline double fsm_percent(double phase, double start, double end) {
+    LMPC_NO_FMA
+    double p = (phase - start) / (end - start);
+    if (p < 0.0) p = 0.0;
+    else if (p > 1.0) p = 1.0;
+    return p;
+}
+
+// BezierUtils::bezier_curve (Utils.cpp:179-192) with the control points of get_foot_pos_curve (:136-176):
+// P = [s, s + c1, f + c2, f, f]; the powers written as products
+LMPC_HD inline double swing_bezier(double t, double s, double f, double c2) {
+    LMPC_NO_FMA
+    const double o = 1.0 - t;
+    const double t2 = t * t, t3 = t2 * t, t4 = t3 * t;
+    const double o2 = o * o, o3 = o2 * o, o4 = o3 * o;
+    double y = 0.0;
+    y += 1.0 * 1.0 * o4 * s;
+    y += 4.0 * t * o3 * s;
+    y += 6.0 * t2 * o2 * (f + c2);
+    y += 4.0 * t3 * o * f;
+    y += 1.0 * t4 * 1.0 * f;
+    return y;
+}
+
+// The plant: the QP's stage-0 transition x+ = A(yaw) x + B u0 - g dt e11 (ConvexQPSolver.cpp:198-228,294-297) on the
+// robot's command state, with the rotation and the body-centred feet that command carries (what the QP saw).
+LMPC_HD inline void plant_step(const PlantParams& p, lmpc_robot& rb, const double u0[12]) {
+    LMPC_NO_FMA
+    lmpc_state_in& st = rb.cmd.state;
+    const double* R = st.root_rot_mat;
+    const double dt = p.dt;
+    // world inertia R Ib R' and its inverse (adjugate)
+    double T[9], Iw[9], Ii[9];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c)
+            T[3 * r + c] = R[3 * r] * p.Ib[c] + R[3 * r + 1] * p.Ib[3 + c] + R[3 * r + 2] * p.Ib[6 + c];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c)
+            Iw[3 * r + c] = T[3 * r] * R[3 * c] + T[3 * r + 1] * R[3 * c + 1] + T[3 * r + 2] * R[3 * c + 2];
+    Ii[0] = Iw[4] * Iw[8] - Iw[5] * Iw[7];
+    Ii[1] = Iw[2] * Iw[7] - Iw[1] * Iw[8];
+    Ii[2] = Iw[1] * Iw[5] - Iw[2] * Iw[4];
+    Ii[3] = Iw[5] * Iw[6] - Iw[3] * Iw[8];
+    Ii[4] = Iw[0] * Iw[8] - Iw[2] * Iw[6];
+    Ii[5] = Iw[2] * Iw[3] - Iw[0] * Iw[5];
+    Ii[6] = Iw[3] * Iw[7] - Iw[4] * Iw[6];
+    Ii[7] = Iw[1] * Iw[6] - Iw[0] * Iw[7];
+    Ii[8] = Iw[0] * Iw[4] - Iw[1] * Iw[3];
+    const double det = Iw[0] * Ii[0] + Iw[1] * Ii[3] + Iw[2] * Ii[6];
+    for (int e = 0; e < 9; ++e) Ii[e] = Ii[e] / det;
+    // sum of r_i x f_i and of f_i
+    double tau[3] = {0.0, 0.0, 0.0}, fs[3] = {0.0, 0.0, 0.0};
+    for (int j = 0; j < 4; ++j) {
+        const double* r = st.foot_pos_abs + 3 * j;
+        const double* f = u0 + 3 * j;
+        tau[0] += r[1] * f[2] - r[2] * f[1];
+        tau[1] += r[2] * f[0] - r[0] * f[2];
+        tau[2] += r[0] * f[1] - r[1] * f[0];
+        for (int k = 0; k < 3; ++k) fs[k] += f[k];
+    }
+    const double cy = cos(st.root_euler[2]), sy = sin(st.root_euler[2]);
+    const double w[3] = {st.root_ang_vel[0], st.root_ang_vel[1], st.root_ang_vel[2]};
+    const double v[3] = {st.root_lin_vel[0], st.root_lin_vel[1], st.root_lin_vel[2]};
+    st.root_euler[0] = st.root_euler[0] + (cy * w[0] + sy * w[1]) * dt;
+    st.root_euler[1] = st.root_euler[1] + (cy * w[1] - sy * w[0]) * dt;
+    st.root_euler[2] = st.root_euler[2] + w[2] * dt;
+    for (int k = 0; k < 3; ++k) {
+        st.root_pos[k] = st.root_pos[k] + v[k] * dt;
+        st.root_ang_vel[k] = w[k] + (Ii[3 * k] * tau[0] + Ii[3 * k + 1] * tau[1] + Ii[3 * k + 2] * tau[2]) * dt;
+        st.root_lin_vel[k] = v[k] + fs[k] * ((1.0 / p.mass) * dt);
+    }
+    st.root_lin_vel[2] = st.root_lin_vel[2] - p.grav * dt;
+    rb.tick += 1;
+}
+
+// The bookkeeping before a QP, in the reference's order (lmpc_rollout.h, lmpc_robot_advance).  target[12]: the
+// Raibert foot_pos_target_world (BaseInterface.cpp:358-399).
+LMPC_HD inline void robot_bookkeep(const lmpc_rollout_cfg& cfg, double dt, lmpc_robot& rb, double target[12]) {
+    LMPC_NO_FMA
+    lmpc_command& c = rb.cmd;
+    lmpc_state_in& st = c.state;
+    // Raibert heuristic from the current state
+    const double cy = cos(st.root_euler[2]), sy = sin(st.root_euler[2]);
+    const double vd[2] = {cy * st.root_lin_vel_d_rel[0] - sy * st.root_lin_vel_d_rel[1],
+                          sy * st.root_lin_vel_d_rel[0] + cy * st.root_lin_vel_d_rel[1]};
+    const double k = sqrt(fabs(st.root_pos[2]) / 9.8);
+    double delta[2];
+    for (int a = 0; a < 2; ++a) {
+        double d = k * (st.root_lin_vel[a] - vd[a]) + (1.0 / c.gait_speed / 2.0) / 2.0 * vd[a];
+        if (d < -cfg.foot_delta_limit[a]) d = -cfg.foot_delta_limit[a];
+        if (d > cfg.foot_delta_limit[a]) d = cfg.foot_delta_limit[a];
+        delta[a] = d;
+    }
+    for (int j = 0; j < 4; ++j) {
+        const double* df = cfg.default_feet + 3 * j;
+        target[3 * j + 0] = (cy * df[0] - sy * df[1]) + delta[0] + st.root_pos[0];
+        target[3 * j + 1] = (sy * df[0] + cy * df[1]) + delta[1] + st.root_pos[1];
+        target[3 * j + 2] = df[2] + st.root_pos[2];
+    }
+    // ConvexMpc.cpp:38
+    st.root_euler_d[2] = st.root_euler_d[2] + st.root_ang_vel_d_rel[2] * dt;
+    // foot_update (ConvexMpc.cpp:80-108) with LeggedContactFSM::update (LeggedContactFSM.cpp:38-84), no foot contact flag
+    for (int j = 0; j < 4; ++j) {
+        double* foot = rb.foot_pos_world + 3 * j;
+        if (c.gait == LMPC_GAIT_STAND) {  // movement mode 0: reset, plan_contacts true
+            c.gait_phase[j] = 0.0;
+            rb.fsm_index[j] = 0;
+            rb.fsm_start[j] = 0.0;
+            c.plan_contacts[j] = 1;
+            continue;
+        }
+        const GaitTab t = gait_table(c.gait, j);
+        double phase = c.gait_phase[j] + c.gait_speed * dt;
+        int idx = rb.fsm_index[j];
+        int s = c.plan_contacts[j] ? 1 : 0;
+        bool enter = false;
+        if (s == 1) enter = phase >= t.sw[idx];
+        else enter = fsm_percent(phase, rb.fsm_start[j], t.sw[idx]) >= 1.0;
+        if (enter) {  // common_enter (LeggedContactFSM.cpp:214-229)
+            const int prev = idx;
+            idx = (idx + 1) % t.size;
+            if (idx < prev) phase -= 1.0;
+            rb.fsm_start[j] = phase;
+            rb.fsm_index[j] = idx;
+            s = 1 - s;
+            if (s == 0) {  // swing_enter
+                for (int a = 0; a < 3; ++a) rb.swing_start_world[3 * j + a] = foot[a];
+            } else {  // stance_enter: the plant lands the foot on the target's x, y
+                foot[0] = target[3 * j + 0];
+                foot[1] = target[3 * j + 1];
+                foot[2] = cfg.ground_z;
+            }
+        }
+        c.gait_phase[j] = phase;
+        c.plan_contacts[j] = (uint8_t)s;
+        if (s == 0) {  // swing_update: get_foot_pos_curve takes its t as a float (Utils.cpp:136)
+            const double tt = (double)(float)fsm_percent(phase, rb.fsm_start[j], t.sw[idx]);
+            const double* ss = rb.swing_start_world + 3 * j;
+            foot[0] = swing_bezier(tt, ss[0], target[3 * j + 0], 0.0);
+            foot[1] = swing_bezier(tt, ss[1], target[3 * j + 1], 0.0);
+            foot[2] = swing_bezier(tt, ss[2], target[3 * j + 2], cfg.swing_clearance);
+        }
+    }
+    euler_zyx_to_rot(st.root_euler[0], st.root_euler[1], st.root_euler[2], st.root_rot_mat);
+    for (int j = 0; j < 4; ++j)
+        for (int a = 0; a < 3; ++a) st.foot_pos_abs[3 * j + a] = rb.foot_pos_world[3 * j + a] - st.root_pos[a];
 }
 
 }  // namespace lmpc_common

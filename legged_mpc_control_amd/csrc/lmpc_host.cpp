@@ -229,6 +229,82 @@ int lmpc_grf_to_torque(const lmpc_leg_kin* k, const double rot[9], const double 
     return LMPC_OK;
 }
 
+// ---- the closed-loop tick on the host (include/lmpc/lmpc_rollout.h) --------
+int lmpc_rollout_abi_version(void) { return LMPC_ROLLOUT_ABI_VERSION; }
+int lmpc_robot_size(void) { return (int)sizeof(lmpc_robot); }
+
+void lmpc_rollout_cfg_go1(lmpc_rollout_cfg* c) {
+    lmpc_synth_cfg s;
+    lmpc_synth_cfg_go1(&s);
+    std::memset(c, 0, sizeof(*c));
+    std::memcpy(c->default_feet, s.default_feet, sizeof(s.default_feet));
+    c->swing_clearance = 0.23f;  // LeggedParams.h:27 defines it as a float
+    c->foot_delta_limit[0] = c->foot_delta_limit[1] = 0.8;
+    c->ground_z = 0.0;
+}
+
+int lmpc_robot_init(const lmpc_rollout_cfg* cfg, const double x0[12], const double vel_d[2], double yaw_rate,
+                    double height, int gait, double gait_speed, lmpc_robot* rb) {
+    if (!cfg || !x0 || !vel_d || !rb || gait < LMPC_GAIT_TROT || gait > LMPC_GAIT_STAND || !(gait_speed > 0.0))
+        return LMPC_ERR_ARG;
+    std::memset(rb, 0, sizeof(*rb));
+    lmpc_state_in& st = rb->cmd.state;
+    for (int k = 0; k < 3; ++k) {
+        st.root_euler[k] = x0[k];
+        st.root_pos[k] = x0[3 + k];
+        st.root_ang_vel[k] = x0[6 + k];
+        st.root_lin_vel[k] = x0[9 + k];
+    }
+    st.root_euler_d[2] = x0[2];
+    st.root_pos_d[2] = height;
+    st.root_lin_vel_d_rel[0] = vel_d[0];
+    st.root_lin_vel_d_rel[1] = vel_d[1];
+    st.root_ang_vel_d_rel[2] = yaw_rate;
+    rb->cmd.gait = gait;
+    rb->cmd.gait_speed = gait_speed;
+    lmpc_common::euler_zyx_to_rot(x0[0], x0[1], x0[2], st.root_rot_mat);
+    const double cy = std::cos(x0[2]), sy = std::sin(x0[2]);
+    for (int j = 0; j < 4; ++j) {
+        const double* df = cfg->default_feet + 3 * j;
+        double* f = rb->foot_pos_world + 3 * j;
+        f[0] = (cy * df[0] - sy * df[1]) + x0[3];
+        f[1] = (sy * df[0] + cy * df[1]) + x0[4];
+        f[2] = cfg->ground_z;
+        for (int a = 0; a < 3; ++a) {
+            rb->swing_start_world[3 * j + a] = f[a];
+            st.foot_pos_abs[3 * j + a] = f[a] - x0[3 + a];
+        }
+        // LeggedContactFSM::reset: phase 0, the pattern's first entry
+        rb->cmd.plan_contacts[j] = (uint8_t)lmpc_common::gait_table(gait, j).state[0];
+    }
+    return LMPC_OK;
+}
+
+static lmpc_common::PlantParams plant_params(const lmpc_params* p) {
+    lmpc_common::PlantParams pp;
+    pp.mass = p->robot_mass;
+    for (int i = 0; i < 9; ++i) pp.Ib[i] = p->trunk_inertia[i];
+    pp.grav = p->gravity;
+    pp.dt = p->dt;
+    return pp;
+}
+
+int lmpc_robot_plant_step(const lmpc_params* p, lmpc_robot* rb, const double u0[12]) {
+    if (!p || !rb || !u0) return LMPC_ERR_ARG;
+    lmpc_common::plant_step(plant_params(p), *rb, u0);
+    return LMPC_OK;
+}
+
+int lmpc_robot_advance(const lmpc_params* p, const lmpc_rollout_cfg* cfg, lmpc_robot* rb, const double* u0,
+                       double* foot_target) {
+    if (!p || !cfg || !rb) return LMPC_ERR_ARG;
+    if (u0) lmpc_common::plant_step(plant_params(p), *rb, u0);
+    double target[12];
+    lmpc_common::robot_bookkeep(*cfg, p->dt, *rb, target);
+    if (foot_target) std::memcpy(foot_target, target, sizeof(target));
+    return LMPC_OK;
+}
+
 int lmpc_synth_normals(uint64_t seed, int64_t first_index, int count, double theta_max, double* normals) {
     if (!normals || count < 0 || !(theta_max >= 0.0) || theta_max >= 1.5707963267948966) return LMPC_ERR_ARG;
     for (int b = 0; b < count; ++b)

@@ -270,6 +270,71 @@ class BatchedConvexQPSolver:
             None if status is None else status.data_ptr(), None if iters is None else iters.data_ptr(),
             self._stream(stream, cmd.device)), "lmpc_solve_commands_device")
 
+    # ---- warm start and the closed-loop rollout on the device (include/lmpc/lmpc_rollout.h) ------------
+    def shift_active_set_device(self, act, stream=None):
+        """uint8 [B, H, 4] active sets in HBM -> the sets one MPC step later (a new tensor; lmpc_shift_active_set_device)."""
+        import torch
+
+        B = act.shape[0]
+        if not act.is_cuda or act.dtype != torch.uint8 or not act.is_contiguous() or tuple(act.shape) != (B, self.H, 4):
+            raise ValueError("act must be a contiguous uint8 device tensor [B, H, 4]")
+        out = torch.empty_like(act)
+        N.check(self._L.lmpc_shift_active_set_device(self._ctx, act.data_ptr(), B, out.data_ptr(),
+                                                     self._stream(stream, act.device)), "lmpc_shift_active_set_device")
+        return out
+
+    def solve_commands_warm_device(self, cmd, grf, act_in=None, act_out=None, status=None, iters=None, stream=None,
+                                   normals=None) -> None:
+        """lmpc_solve_batch_warm on device buffers: commands -> records -> the scratch Riccati kernel from act_in
+        (uint8 [B, H, 4] or None = cold), the verified sets into act_out (or None); asynchronous on `stream`."""
+        import torch
+
+        B = cmd.shape[0]
+        if not cmd.is_cuda or cmd.dtype != torch.uint8 or tuple(cmd.shape) != (B, N.COMMAND_BYTES) or \
+                not cmd.is_contiguous():
+            raise ValueError("commands must be a contiguous uint8 device tensor [B, COMMAND_BYTES]")
+        if grf.shape != (B, self.H, 12) or grf.dtype != torch.float64 or not grf.is_cuda or not grf.is_contiguous():
+            raise ValueError("bad grf tensor")
+        for a in (act_in, act_out):
+            if a is not None and (not a.is_cuda or a.dtype != torch.uint8 or not a.is_contiguous() or
+                                  tuple(a.shape) != (B, self.H, 4)):
+                raise ValueError("active sets must be contiguous uint8 device tensors [B, H, 4]")
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        N.check(self._L.lmpc_solve_commands_warm_device(
+            self._ctx, cmd.data_ptr(), ptr(normals), B, ptr(act_in), ptr(act_out), grf.data_ptr(), ptr(status),
+            ptr(iters), self._stream(stream, cmd.device)), "lmpc_solve_commands_warm_device")
+
+    def rollout_device(self, robots, ticks: int, act=None, log=False, stream=None, cfg=None):
+        """`ticks` closed-loop MPC ticks for the robots (uint8 device tensor [B, ROBOT_BYTES], updated in place;
+        rollout.robots_init / rollout.to_device), asynchronous on `stream` with no host synchronisation between ticks
+        (lmpc_rollout_device).  act: uint8 [B, H, 4] active sets carried between ticks and calls (read and written;
+        zeros = nothing known) for warm solves on the scratch Riccati kernel, None = cold solves on the context's
+        routing.  log: True -> a rollout.RolloutLog of new tensors is filled and returned; a RolloutLog -> that one;
+        False -> None.  cfg: LmpcRolloutCfg (default Go1)."""
+        import torch
+
+        from . import rollout as R
+
+        B = robots.shape[0]
+        if not robots.is_cuda or robots.dtype != torch.uint8 or not robots.is_contiguous() or \
+                tuple(robots.shape) != (B, N.ROBOT_BYTES):
+            raise ValueError("robots must be a contiguous uint8 device tensor [B, ROBOT_BYTES]")
+        if act is not None and (not act.is_cuda or act.dtype != torch.uint8 or not act.is_contiguous() or
+                                tuple(act.shape) != (B, self.H, 4)):
+            raise ValueError("act must be a contiguous uint8 device tensor [B, H, 4]")
+        if cfg is None:
+            cfg = R.cfg_go1()
+        if log is True:
+            log = R.alloc_log(int(ticks), B, robots.device)
+        lg = log.struct() if log else None
+        if log and (log.x.shape[0] < ticks or log.x.shape[1] != B):
+            raise ValueError("the log holds fewer ticks than asked for, or another batch")
+        N.check(self._L.lmpc_rollout_device(self._ctx, ctypes.byref(cfg), robots.data_ptr(),
+                                            None if act is None else act.data_ptr(), B, int(ticks),
+                                            None if lg is None else ctypes.byref(lg),
+                                            self._stream(stream, robots.device)), "lmpc_rollout_device")
+        return log or None
+
     # ---- the step after the QP: GRF -> joint torque (SURVEY.md 8f-2) ------------------------------
     def grf_to_torque_device(self, kin: N.LmpcLegKin, rec, joint_pos, grf, stream=None):
         """tau [B, 12] = -J'(R'u0) per leg, from rec (R), joint_pos [B, 12] and grf [B, H, 12] in HBM."""

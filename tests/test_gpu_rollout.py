@@ -1,0 +1,264 @@
+"""GPU tests of the device-resident closed-loop rollout (include/lmpc/lmpc_rollout.h): every tick against the CPU
+oracle and the host tick, the warm start carried on the device, chaining, batch independence, the end-to-end
+fixture of tests/golden/make_rollout_golden.py, argument handling and ordering."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+
+import rollout_ref as RR
+from conftest import GOLDEN, rel_err
+
+from legged_mpc_control_amd import BatchedConvexQPSolver, _native as N, rollout as R, synth
+from oracle import fsm as F
+from oracle import oracle as O
+
+pytestmark = pytest.mark.gpu
+
+CHECK_TICKS = (0, 1, 11, 12, 13, 14, 24, 25, 26, 29)  # a swing entry, a touchdown and a phase wrap at gait speed 4.0
+
+
+@pytest.fixture(scope="module")
+def dev():
+    import torch
+
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    return torch.device("cuda:0")
+
+
+def standing(yaw=0.0):
+    x0 = np.zeros(12)
+    x0[2], x0[5] = yaw, 0.30
+    return x0
+
+
+def mixed_robots(n_trot, others, seed):
+    """n_trot trot robots with seeded commands, then `others` = [(gait, vel_d, yaw_rate), ...]; -> (array, is_trot)."""
+    rng = np.random.default_rng(seed)
+    cfg = R.cfg_go1()
+    specs = [(F.TROT, (rng.uniform(-0.6, 0.6), rng.uniform(-0.3, 0.3)), rng.uniform(-0.5, 0.5)) for _ in range(n_trot)]
+    specs += list(others)
+    arr = (N.LmpcRobot * len(specs))()
+    for b, (gait, vd, yr) in enumerate(specs):
+        arr[b] = R.robot_init(cfg, standing(rng.uniform(-3.0, 3.0)), vd, yr, 0.30, gait, 4.0)
+    return arr, np.array([s[0] == F.TROT for s in specs])
+
+
+def robots37():
+    others = [(F.CRAWL, (0.2, 0.0), 0.1), (F.CRAWL, (-0.1, 0.1), 0.0), (F.TROT_WITH_STAND, (0.3, 0.0), 0.0),
+              (F.TROT_WITH_STAND, (0.0, 0.1), -0.2), (F.STAND, (0.0, 0.0), 0.0), (F.STAND, (0.0, 0.0), 0.0),
+              (F.TROT, (0.0, 0.0), 0.0), (F.TROT, (0.0, 0.0), 0.0)]
+    return mixed_robots(29, others, seed=37)
+
+
+def run(dev, H, robots, ticks, warm=False, chunks=None, stream=None, solver=None):
+    """-> dict(robots uint8 [B, 656], act uint8 [B, H, 4] or None, and the logs as NumPy [sum(chunks), B, ...])."""
+    import torch
+
+    s = solver or BatchedConvexQPSolver(synth.params(), H, max_batch=0)
+    d_rb = R.to_device(robots, dev)
+    B = d_rb.shape[0]
+    act = torch.zeros((B, H, 4), dtype=torch.uint8, device=dev) if warm else None
+    logs = [s.rollout_device(d_rb, n, act=act, log=True, stream=stream) for n in (chunks or [ticks])]
+    torch.cuda.synchronize()
+    out = {k: np.concatenate([lg.numpy()[k] for lg in logs]) for k in ("cmd", "u0", "x", "status", "iters")}
+    out["cmd_bytes"] = np.concatenate([lg.cmd.cpu().numpy() for lg in logs])
+    out["robots"] = d_rb.cpu().numpy()
+    out["act"] = None if act is None else act.cpu().numpy()
+    return out
+
+
+@pytest.fixture(scope="module")
+def cold37(dev):
+    robots, is_trot = robots37()
+    return robots, is_trot, run(dev, 10, robots, 30)
+
+
+def check_ticks(H, robots, is_trot, out, ticks, check):
+    """Every logged u_0 is the oracle's optimum of the logged command's record (ticks in `check`); every logged command
+    is the host tick from the previous robot and the logged u_0 (every tick); the FSM fields bit for bit."""
+    p, cfg = synth.params(), R.cfg_go1()
+    op = O.params_from(p)
+    B = len(robots)
+    cmds = R.commands_from(out["cmd_bytes"])
+    assert (out["status"][:, is_trot] == 0).all()
+    # the oracle's optimum
+    recs, cons = [], []
+    for t in check:
+        for b in range(B):
+            r, c = synth.command_to_record(p, H, cmds[t * B + b])
+            recs.append(r)
+            cons.append(c)
+    ref, _, fails = O.solve_batch(op, H, np.array(recs), np.array(cons), n_threads=8)
+    assert fails == 0
+    got = out["u0"][list(check)].reshape(-1, 12)
+    err = rel_err(got, ref[:, 0])
+    print(f"H={H}: u_0 vs oracle over {len(recs)} QPs: max rel err {err:.2e}")
+    assert err <= 1e-7
+    # the host tick
+    shadow = (N.LmpcRobot * B).from_buffer_copy(bytes(robots))
+    worst = 0.0
+    for t in range(ticks):
+        for b in range(B):
+            rb = shadow[b]
+            R.advance(p, cfg, rb, out["u0"][t - 1, b] if t else None)
+            lg = cmds[t * B + b]
+            assert list(rb.cmd.gait_phase) == list(lg.gait_phase), (t, b)
+            assert list(rb.cmd.plan_contacts) == list(lg.plan_contacts), (t, b)
+            assert rb.cmd.gait == lg.gait and rb.cmd.gait_speed == lg.gait_speed
+            a = np.frombuffer(bytes(rb.cmd.state), dtype=np.float64)
+            g = np.frombuffer(bytes(lg.state), dtype=np.float64)
+            worst = max(worst, float(np.max(np.abs(a - g) / np.maximum(1.0, np.abs(a)))))
+            shadow[b].cmd = lg  # the next tick starts from the logged command
+    print(f"H={H}: logged commands vs the host tick: max rel err {worst:.2e}")
+    assert worst <= 1e-12
+    # the logged state is the plant step, and the robots the call leaves are those after the last one
+    fin = R.robots_view(out["robots"])
+    for b in range(B):
+        R.plant_step(p, shadow[b], out["u0"][ticks - 1, b])
+        want = R.robots_view(R.to_bytes((N.LmpcRobot * 1)(shadow[b])))[0]
+        assert np.array_equal(fin[b]["fsm_index"], want["fsm_index"]) and np.array_equal(fin[b]["fsm_start"], want["fsm_start"])
+        assert fin[b]["tick"] == want["tick"] == ticks
+        for k in ("euler", "pos", "omega", "vel", "foot_pos_world", "swing_start_world"):
+            assert rel_err(fin[b][k], want[k]) <= 1e-12, (b, k)
+        assert np.array_equal(out["x"][ticks - 1, b], np.concatenate([fin[b][k] for k in ("euler", "pos", "omega", "vel")]))
+
+
+def test_per_tick_parity_dense_path(cold37):
+    robots, is_trot, out = cold37
+    gp = R.commands_view(out["cmd_bytes"])["plan_contacts"]
+    assert (gp[0] != gp[13]).any() and (gp[13] != gp[26]).any()  # the legs did change state between the checked ticks
+    check_ticks(10, robots, is_trot, out, 30, CHECK_TICKS)
+
+
+def test_per_tick_parity_lds_riccati(dev):
+    robots, is_trot = mixed_robots(3, [(F.CRAWL, (0.2, 0.0), 0.1), (F.STAND, (0.0, 0.0), 0.0)], seed=20)
+    s = BatchedConvexQPSolver(synth.params(), 20, max_batch=0)
+    assert s.dense_path == "off" and s.riccati_path == "lds"
+    out = run(dev, 20, robots, 15, solver=s)
+    check_ticks(20, robots, is_trot, out, 15, range(15))
+
+
+def test_warm_start_carried_on_the_device(dev, cold37):
+    import torch
+
+    robots, is_trot, cold = cold37
+    warm = run(dev, 10, robots, 30, warm=True)
+    err = rel_err(warm["u0"], cold["u0"])
+    it_w, it_c = int((warm["iters"][1:] & 0xFFFF).sum()), int((cold["iters"][1:] & 0xFFFF).sum())
+    print(f"warm vs cold u_0: max rel err {err:.2e}; interior-point iterations over ticks 1-29: warm {it_w}, cold {it_c}")
+    assert err <= 1e-7
+    assert (warm["status"][:, is_trot] == 0).all()
+    assert it_w < it_c
+    # the device forms of lmpc_solve_batch_warm and lmpc_shift_active_set against the host ones, two ticks in a row
+    p, H, B = synth.params(), 10, len(robots)
+    s = BatchedConvexQPSolver(p, H, max_batch=B)
+    cmds = R.commands_from(cold["cmd_bytes"])
+    act_h = act_d = None
+    for t in (12, 13):
+        rc = [synth.command_to_record(p, H, cmds[t * B + b]) for b in range(B)]
+        rec, con = np.array([r for r, _ in rc]), np.array([c for _, c in rc])
+        grf_h, st_h, _, act_h = s.solve_warm(rec, con, act_h)
+        d_cmd = torch.from_numpy(cold["cmd_bytes"][t].copy()).to(dev)
+        grf = torch.zeros((B, H, 12), dtype=torch.float64, device=dev)
+        st = torch.zeros(B, dtype=torch.int32, device=dev)
+        act_out = torch.zeros((B, H, 4), dtype=torch.uint8, device=dev)
+        s.solve_commands_warm_device(d_cmd, grf, act_in=act_d, act_out=act_out, status=st)
+        torch.cuda.synchronize()
+        assert rel_err(grf.cpu().numpy(), grf_h) <= 1e-9
+        assert np.array_equal(st.cpu().numpy(), st_h)
+        assert np.array_equal(act_out.cpu().numpy(), act_h)
+        act_h = BatchedConvexQPSolver.shift_active_set(act_h)
+        act_d = s.shift_active_set_device(act_out)
+        torch.cuda.synchronize()
+        assert np.array_equal(act_d.cpu().numpy(), act_h)
+    assert act_h.any()
+
+
+@pytest.mark.parametrize("warm", [False, True])
+def test_chaining(dev, cold37, warm):
+    robots, _, cold = cold37
+    one = run(dev, 10, robots, 30, warm=True) if warm else cold
+    two = run(dev, 10, robots, 30, warm=warm, chunks=[13, 17])
+    for k in ("robots", "cmd_bytes", "u0", "x", "status", "iters"):
+        assert np.array_equal(one[k], two[k]), k
+    if warm:
+        assert np.array_equal(one["act"], two["act"]) and one["act"].any()
+
+
+def test_batch_independence(dev):
+    """Robots 0-4 of a 300-robot rollout equal the same five run alone, bit for bit (both batches within 4 x CUs: the
+    same kernel instances)."""
+    robots, _ = mixed_robots(296, [(F.CRAWL, (0.2, 0.0), 0.1), (F.TROT_WITH_STAND, (0.3, 0.0), 0.0),
+                                   (F.STAND, (0.0, 0.0), 0.0), (F.TROT, (0.0, 0.0), 0.0)], seed=300)
+    big = run(dev, 10, robots, 30)
+    five = (N.LmpcRobot * 5).from_buffer_copy(bytes(robots)[:5 * N.ROBOT_BYTES])
+    small = run(dev, 10, five, 30)
+    assert np.array_equal(big["robots"][:5], small["robots"])
+    for k in ("cmd_bytes", "u0", "x", "status", "iters"):
+        assert np.array_equal(big[k][:, :5], small[k]), k
+    assert (big["status"][:, :296] == 0).all()
+
+
+@pytest.mark.parametrize("warm", [False, True])
+def test_end_to_end_against_the_cpu(dev, warm):
+    """The golden robots (4 trot robots, H = 10, 60 ticks): every tick's state within 10 x the fixture's `sens` (the
+    state response to a u_0 error at the suite's 1e-7 guard) of the CPU loop, and the tracking caps of the CPU
+    closed-loop test, which the fixture itself meets at tick 60 with margin (velocity within 0.016 m/s, yaw rate
+    within 1e-5 rad/s, height within 0.0024 m, roll / pitch 0.0118 rad), so they are taken unscaled."""
+    g = np.load(os.path.join(GOLDEN, "rollout_trot_h10.npz"))
+    H, ticks = int(g["H"]), int(g["ticks"])
+    cfg = R.cfg_go1()
+    robots = R.robots_init(cfg, standing()[None].repeat(len(g["sens"]), 0), g["vel_d"], g["yaw_rate"], 0.30, F.TROT, 4.0)
+    out = run(dev, H, robots, ticks, warm=warm)
+    assert (out["status"] == 0).all()
+    dev_b = np.abs(out["x"] - g["x"]).max(axis=(0, 2))
+    print(f"warm={warm}: GPU deviation from the CPU loop per robot {dev_b}, sens {g['sens']}")
+    assert (dev_b <= 10.0 * g["sens"]).all()
+    x = out["x"]
+    assert np.abs(x[:, :, 5] - 0.30).max() <= 0.01 and np.abs(x[:, :, 0:2]).max() <= 0.03
+    c, s = np.cos(x[-1, :, 2]), np.sin(x[-1, :, 2])
+    vb = np.stack([c * x[-1, :, 9] + s * x[-1, :, 10], -s * x[-1, :, 9] + c * x[-1, :, 10]], axis=1)
+    assert np.abs(vb - g["vel_d"]).max() <= 0.05
+    assert np.abs(x[-1, :, 8] - g["yaw_rate"]).max() <= 0.03
+
+
+def test_arguments_and_ordering(dev, cold37):
+    import torch
+
+    robots, _, cold = cold37
+    L = N.lib()
+    p, H = synth.params(), 10
+    s = BatchedConvexQPSolver(p, H, max_batch=64)
+    cfg = R.cfg_go1()
+    d_rb = R.to_device(robots, dev)
+    before = d_rb.clone()
+    ctx, rp, cp = s._ctx, d_rb.data_ptr(), ctypes.byref(cfg)
+    assert L.lmpc_rollout_device(None, cp, rp, None, 37, 1, None, None) == -1
+    assert L.lmpc_rollout_device(ctx, None, rp, None, 37, 1, None, None) == -1
+    assert L.lmpc_rollout_device(ctx, cp, None, None, 37, 1, None, None) == -1
+    assert L.lmpc_rollout_device(ctx, cp, rp, None, -1, 1, None, None) == -1
+    assert L.lmpc_rollout_device(ctx, cp, rp, None, 37, -1, None, None) == -1
+    assert L.lmpc_shift_active_set_device(ctx, rp, 1, rp, None) == -1  # aliased
+    assert L.lmpc_shift_active_set_device(None, rp, 1, rp, None) == -1
+    assert L.lmpc_solve_commands_warm_device(ctx, None, None, 1, None, None, None, None, None, None) == -1
+    if torch.cuda.device_count() > 1:
+        other = torch.cuda.Stream(device=1)
+        assert L.lmpc_rollout_device(ctx, cp, rp, None, 37, 1, None, other.cuda_stream) == -1
+    # the two no-ops
+    assert L.lmpc_rollout_device(ctx, cp, rp, None, 37, 0, None, None) == 0
+    assert L.lmpc_rollout_device(ctx, cp, rp, None, 0, 5, None, None) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(d_rb, before)
+    # ordering: a rollout on a caller's stream, then a host-pointer solve on the same context
+    _, _, rec, con = synth.config_batch(2, count=64)
+    want = BatchedConvexQPSolver(p, H, max_batch=64).solve(rec, con)
+    stream = torch.cuda.Stream(device=dev)
+    stream.wait_stream(torch.cuda.current_stream(dev))
+    log = s.rollout_device(d_rb, 30, log=True, stream=stream)
+    got = s.solve(rec, con)
+    torch.cuda.synchronize()
+    for a, b in zip(got, want):
+        assert np.array_equal(a, b)
+    assert np.array_equal(log.u0.cpu().numpy(), cold["u0"]) and np.array_equal(d_rb.cpu().numpy(), cold["robots"])

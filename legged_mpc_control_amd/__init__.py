@@ -7,10 +7,12 @@ include/lmpc/lmpc.h.
 """
 from . import _native
 from ._native import (GAIT_CRAWL, GAIT_STAND, GAIT_TROT, GAIT_TROT_WITH_STAND, LmpcCommand, LmpcLegKin,
-                      LmpcOptions, LmpcParams, LmpcRobot, LmpcRolloutCfg, LmpcRolloutLog, NativeLibraryError)
+                      LmpcOptions, LmpcParams, LmpcRbdModel, LmpcRbdState, LmpcRbdTerms, LmpcRobot, LmpcRolloutCfg,
+                      LmpcRolloutLog, LmpcWbcTarget, NativeLibraryError)
 from .solver import (BatchedConvexQPSolver, ConvexQPSolver, LeggedContactFSM, LeggedCtrl, LeggedFeedback,
                      LeggedParam, LeggedState, foot_jacobian, grf_to_torque, leg_kin_default, solver_options)
-from . import rollout, synth
+from . import rbd, rollout, synth
+from .rbd import WbcPipeline
 
 __all__ = [
     "BatchedConvexQPSolver", "ConvexQPSolver", "LeggedContactFSM", "LeggedState", "LeggedFeedback",
@@ -18,4 +20,5 @@ __all__ = [
     "GAIT_TROT", "GAIT_CRAWL", "GAIT_TROT_WITH_STAND", "GAIT_STAND", "LmpcCommand", "LmpcLegKin",
     "leg_kin_default", "foot_jacobian", "grf_to_torque", "solver_options",
     "rollout", "LmpcRobot", "LmpcRolloutCfg", "LmpcRolloutLog",
+    "rbd", "WbcPipeline", "LmpcRbdModel", "LmpcRbdState", "LmpcRbdTerms", "LmpcWbcTarget",
 ]

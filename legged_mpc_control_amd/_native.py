@@ -62,6 +62,13 @@ ROLLOUT_SYMBOLS = (
     "lmpc_robot_advance", "lmpc_shift_active_set_device", "lmpc_solve_commands_warm_device", "lmpc_rollout_device",
 )
 ROLLOUT_ABI_VERSION = 1
+# include/lmpc/lmpc_rbd.h: floating-base rigid-body dynamics for the WBC (robot state -> lmpc_wbc_input)
+RBD_SYMBOLS = (
+    "lmpc_rbd_abi_version", "lmpc_rbd_model_size", "lmpc_rbd_state_size", "lmpc_wbc_target_size", "lmpc_rbd_terms_size",
+    "lmpc_rbd_model_go1", "lmpc_rbd_model_a1", "lmpc_wbc_target_default", "lmpc_rbd_compute",
+    "lmpc_wbc_input_from_state", "lmpc_wbc_inputs_device", "lmpc_rbd_compute_device",
+)
+RBD_ABI_VERSION = 1
 
 
 class LmpcParams(ctypes.Structure):
@@ -189,6 +196,36 @@ class LmpcWbcInput(ctypes.Structure):
         ("dJv", ctypes.c_double * 12), ("base_accel", ctypes.c_double * 6), ("swing_acc", ctypes.c_double * 12),
         ("forces_des", ctypes.c_double * 12), ("torque_limits", ctypes.c_double * 3), ("mu", ctypes.c_double),
         ("contact", ctypes.c_int32 * 4),
+    ]
+
+
+class LmpcRbdModel(ctypes.Structure):
+    _fields_ = [
+        ("mass", ctypes.c_double * 13), ("com", (ctypes.c_double * 3) * 13), ("inertia", (ctypes.c_double * 6) * 13),
+        ("joint_origin", (ctypes.c_double * 3) * 12), ("foot", (ctypes.c_double * 3) * 4), ("gravity", ctypes.c_double),
+    ]
+
+
+class LmpcRbdState(ctypes.Structure):
+    _fields_ = [
+        ("euler", ctypes.c_double * 3), ("pos", ctypes.c_double * 3), ("joint_pos", ctypes.c_double * 12),
+        ("omega", ctypes.c_double * 3), ("lin_vel", ctypes.c_double * 3), ("joint_vel", ctypes.c_double * 12),
+    ]
+
+
+class LmpcWbcTarget(ctypes.Structure):
+    _fields_ = [
+        ("forces_des", ctypes.c_double * 12), ("foot_pos_des", ctypes.c_double * 12),
+        ("foot_vel_des", ctypes.c_double * 12), ("torque_limits", ctypes.c_double * 3), ("mu", ctypes.c_double),
+        ("swing_kp", ctypes.c_double), ("swing_kd", ctypes.c_double), ("contact", ctypes.c_int32 * 4),
+    ]
+
+
+class LmpcRbdTerms(ctypes.Structure):
+    _fields_ = [
+        ("M", ctypes.c_double * 324), ("nle", ctypes.c_double * 18), ("J", ctypes.c_double * 216),
+        ("dJv", ctypes.c_double * 12), ("foot_pos", ctypes.c_double * 12), ("foot_vel", ctypes.c_double * 12),
+        ("com", ctypes.c_double * 3), ("Ab", ctypes.c_double * 36), ("mass", ctypes.c_double),
     ]
 
 
@@ -350,6 +387,29 @@ def lib():
         L.lmpc_rollout_device.argtypes = [vp, rcp, vp, vp, ctypes.c_int, ctypes.c_int,
                                           ctypes.POINTER(LmpcRolloutLog), vp]
         L.lmpc_rollout_device.restype = ctypes.c_int
+        mp, sp, tp = ctypes.POINTER(LmpcRbdModel), ctypes.POINTER(LmpcRbdState), ctypes.POINTER(LmpcWbcTarget)
+        for name in ("lmpc_rbd_abi_version", "lmpc_rbd_model_size", "lmpc_rbd_state_size", "lmpc_wbc_target_size",
+                     "lmpc_rbd_terms_size"):
+            getattr(L, name).restype = ctypes.c_int
+        L.lmpc_rbd_model_go1.argtypes = [mp]
+        L.lmpc_rbd_model_go1.restype = None
+        L.lmpc_rbd_model_a1.argtypes = [mp]
+        L.lmpc_rbd_model_a1.restype = None
+        L.lmpc_wbc_target_default.argtypes = [tp]
+        L.lmpc_wbc_target_default.restype = None
+        L.lmpc_rbd_compute.argtypes = [mp, sp, ctypes.POINTER(LmpcRbdTerms)]
+        L.lmpc_rbd_compute.restype = ctypes.c_int
+        L.lmpc_wbc_input_from_state.argtypes = [mp, sp, tp, ctypes.POINTER(LmpcWbcInput)]
+        L.lmpc_wbc_input_from_state.restype = ctypes.c_int
+        L.lmpc_wbc_inputs_device.argtypes = [mp, vp, vp, ctypes.c_int, vp, vp]
+        L.lmpc_wbc_inputs_device.restype = ctypes.c_int
+        L.lmpc_rbd_compute_device.argtypes = [mp, vp, ctypes.c_int, vp, vp]
+        L.lmpc_rbd_compute_device.restype = ctypes.c_int
+        sizes = (L.lmpc_rbd_model_size(), L.lmpc_rbd_state_size(), L.lmpc_wbc_target_size(), L.lmpc_rbd_terms_size())
+        mirrors = tuple(ctypes.sizeof(c) for c in (LmpcRbdModel, LmpcRbdState, LmpcWbcTarget, LmpcRbdTerms))
+        if L.lmpc_rbd_abi_version() != RBD_ABI_VERSION or sizes != mirrors:
+            raise NativeLibraryError(f"{path}: lmpc_rbd.h ABI {L.lmpc_rbd_abi_version()} with struct sizes {sizes}, "
+                                     f"this binding is ABI {RBD_ABI_VERSION} with {mirrors}")
         if L.lmpc_rollout_abi_version() != ROLLOUT_ABI_VERSION or L.lmpc_robot_size() != ROBOT_BYTES:
             raise NativeLibraryError(f"{path}: lmpc_rollout.h ABI {L.lmpc_rollout_abi_version()} / lmpc_robot of "
                                      f"{L.lmpc_robot_size()} B, this binding is ABI {ROLLOUT_ABI_VERSION} / {ROBOT_BYTES} B")

@@ -8,11 +8,12 @@ include/lmpc/lmpc.h.
 from . import _native
 from ._native import (GAIT_CRAWL, GAIT_STAND, GAIT_TROT, GAIT_TROT_WITH_STAND, LmpcCommand, LmpcLegKin,
                       LmpcOptions, LmpcParams, LmpcRbdModel, LmpcRbdState, LmpcRbdTerms, LmpcRobot, LmpcRolloutCfg,
-                      LmpcRolloutLog, LmpcWbcTarget, NativeLibraryError)
+                      LmpcRolloutLog, LmpcSimCfg, LmpcSimOut, LmpcWbcTarget, NativeLibraryError)
 from .solver import (BatchedConvexQPSolver, ConvexQPSolver, LeggedContactFSM, LeggedCtrl, LeggedFeedback,
                      LeggedParam, LeggedState, foot_jacobian, grf_to_torque, leg_kin_default, solver_options)
-from . import rbd, rollout, synth
+from . import rbd, rollout, sim, synth
 from .rbd import WbcPipeline
+from .sim import WbcSim
 
 __all__ = [
     "BatchedConvexQPSolver", "ConvexQPSolver", "LeggedContactFSM", "LeggedState", "LeggedFeedback",
@@ -21,4 +22,5 @@ __all__ = [
     "leg_kin_default", "foot_jacobian", "grf_to_torque", "solver_options",
     "rollout", "LmpcRobot", "LmpcRolloutCfg", "LmpcRolloutLog",
     "rbd", "WbcPipeline", "LmpcRbdModel", "LmpcRbdState", "LmpcRbdTerms", "LmpcWbcTarget",
+    "sim", "WbcSim", "LmpcSimCfg", "LmpcSimOut",
 ]

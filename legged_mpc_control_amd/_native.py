@@ -69,6 +69,12 @@ RBD_SYMBOLS = (
     "lmpc_wbc_input_from_state", "lmpc_wbc_inputs_device", "lmpc_rbd_compute_device",
 )
 RBD_ABI_VERSION = 1
+# include/lmpc/lmpc_sim.h: the rigid-body plant (torques and a contact set -> accelerations, forces, next state)
+SIM_SYMBOLS = (
+    "lmpc_sim_abi_version", "lmpc_sim_cfg_size", "lmpc_sim_out_size", "lmpc_sim_cfg_default", "lmpc_sim_work_bytes",
+    "lmpc_rbd_forward_dynamics", "lmpc_sim_step", "lmpc_rbd_forward_dynamics_device", "lmpc_sim_step_device",
+)
+SIM_ABI_VERSION = 1
 
 
 class LmpcParams(ctypes.Structure):
@@ -226,6 +232,19 @@ class LmpcRbdTerms(ctypes.Structure):
         ("M", ctypes.c_double * 324), ("nle", ctypes.c_double * 18), ("J", ctypes.c_double * 216),
         ("dJv", ctypes.c_double * 12), ("foot_pos", ctypes.c_double * 12), ("foot_vel", ctypes.c_double * 12),
         ("com", ctypes.c_double * 3), ("Ab", ctypes.c_double * 36), ("mass", ctypes.c_double),
+    ]
+
+
+class LmpcSimCfg(ctypes.Structure):
+    _fields_ = [("dt", ctypes.c_double), ("ground_z", ctypes.c_double), ("unilateral", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class LmpcSimOut(ctypes.Structure):
+    _fields_ = [
+        ("qdd", ctypes.c_double * 18), ("force", ctypes.c_double * 12), ("foot_pos", ctypes.c_double * 12),
+        ("foot_vel", ctypes.c_double * 12), ("held", ctypes.c_int32 * 4), ("touch", ctypes.c_int32 * 4),
+        ("status", ctypes.c_int32), ("reserved", ctypes.c_int32),
     ]
 
 
@@ -410,6 +429,28 @@ def lib():
         if L.lmpc_rbd_abi_version() != RBD_ABI_VERSION or sizes != mirrors:
             raise NativeLibraryError(f"{path}: lmpc_rbd.h ABI {L.lmpc_rbd_abi_version()} with struct sizes {sizes}, "
                                      f"this binding is ABI {RBD_ABI_VERSION} with {mirrors}")
+        cfp, sop = ctypes.POINTER(LmpcSimCfg), ctypes.POINTER(LmpcSimOut)
+        for name in ("lmpc_sim_abi_version", "lmpc_sim_cfg_size", "lmpc_sim_out_size"):
+            getattr(L, name).restype = ctypes.c_int
+        L.lmpc_sim_cfg_default.argtypes = [cfp]
+        L.lmpc_sim_cfg_default.restype = None
+        L.lmpc_sim_work_bytes.argtypes = [ctypes.c_int]
+        L.lmpc_sim_work_bytes.restype = ctypes.c_size_t
+        L.lmpc_rbd_forward_dynamics.argtypes = [mp, sp, dp, i32p, ctypes.c_int, sop]
+        L.lmpc_rbd_forward_dynamics.restype = ctypes.c_int
+        L.lmpc_sim_step.argtypes = [mp, cfp, sp, dp, i32p, sp, sop]
+        L.lmpc_sim_step.restype = ctypes.c_int
+        L.lmpc_rbd_forward_dynamics_device.argtypes = [mp, vp, vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int,
+                                                       ctypes.c_int, vp, vp]
+        L.lmpc_rbd_forward_dynamics_device.restype = ctypes.c_int
+        L.lmpc_sim_step_device.argtypes = [mp, cfp, vp, vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int,
+                                           ctypes.c_int, vp, vp, vp, ctypes.c_size_t, vp]
+        L.lmpc_sim_step_device.restype = ctypes.c_int
+        sim_sizes = (L.lmpc_sim_cfg_size(), L.lmpc_sim_out_size())
+        sim_mirrors = (ctypes.sizeof(LmpcSimCfg), ctypes.sizeof(LmpcSimOut))
+        if L.lmpc_sim_abi_version() != SIM_ABI_VERSION or sim_sizes != sim_mirrors:
+            raise NativeLibraryError(f"{path}: lmpc_sim.h ABI {L.lmpc_sim_abi_version()} with struct sizes {sim_sizes}, "
+                                     f"this binding is ABI {SIM_ABI_VERSION} with {sim_mirrors}")
         if L.lmpc_rollout_abi_version() != ROLLOUT_ABI_VERSION or L.lmpc_robot_size() != ROBOT_BYTES:
             raise NativeLibraryError(f"{path}: lmpc_rollout.h ABI {L.lmpc_rollout_abi_version()} / lmpc_robot of "
                                      f"{L.lmpc_robot_size()} B, this binding is ABI {ROLLOUT_ABI_VERSION} / {ROBOT_BYTES} B")

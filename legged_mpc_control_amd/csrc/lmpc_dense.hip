@@ -8,9 +8,10 @@
 // Condensation (once per QP, ConvexQPSolver.cpp:198-313 restated in condensed form):
 //   free response  c_{m+1} = A_m c_m - g dt e11,  c_0 = x0
 //   adjoint        mu_m = Q (c_m - xref_{m-1}) + A_m' mu_{m+1}          -> g_i = B' mu_{i+1}
-//   cost-to-go     P~_H = Q,  P~_m = Q + A_m' P~_{m+1} A_m              (fp64 MFMA, 12x12)
+//   cost-to-go     P~_H = Q,  P~_m = Q + A_m' P~_{m+1} A_m
 //   Hessian        H[i][j] = B' (A_j ... A_{i+1})' P~_{j+1} B  (i <= j), + R on the diagonal blocks,
 //                  one column per lane: L = P~_{j+1} B e_c, then L <- A_{i+1}' L down the steps.
+// (the first three as sums over the steps, not recursions: lmpc_dense_common.h)
 // Variables are laid out 5 leg-steps (15 variables + 1 padding slot) per 16-wide tile, so every
 // 3x3 leg block sits inside one tile and N <= 64 fits 4x4 tiles.  H is kept in LDS as its upper
 // tiles in the MFMA accumulator layout (lane l, register i <-> row (l>>4)+4i, column l&15).
@@ -118,8 +119,7 @@ extern "C" int lmpc_debug_dense_stamps(unsigned long long* out, int nqp) {
 #endif
 
 size_t dense_lds_bytes(int H) {
-    const int scr = 72 * H > DN_SCR_MIN ? 72 * H : DN_SCR_MIN;
-    const int doubles = 40 + 72 + 24 + 36 + 10 * DN_TILE + 64 * 3 + 180 + 20 + 60 + 64 + 2 * H + 12 * H + 12 * H + 64 + scr;
+    const int doubles = 40 + 72 + 24 + 36 + 10 * DN_TILE + 64 * 3 + 180 + 60 + 64 + 2 * H + 12 * H + 64 + DN_SCR_MIN;
     return (size_t)doubles * sizeof(double) + (20 + 33) * sizeof(int);
 }
 

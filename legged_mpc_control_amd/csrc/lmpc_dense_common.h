@@ -11,9 +11,13 @@
 // and condensation (ConvexQPSolver.cpp:254-313 in condensed form):
 //   free response  c_{m+1} = A_m c_m - g dt e11,  c_0 = x0
 //   adjoint        mu_m = Q (c_m - xref_{m-1}) + A_m' mu_{m+1}          -> g_i = B' mu_{i+1}
-//   cost-to-go     P~_H = Q,  P~_m = Q + A_m' P~_{m+1} A_m              (fp64 MFMA, 12x12)
+//   cost-to-go     P~_H = Q,  P~_m = Q + A_m' P~_{m+1} A_m
 //   Hessian        H[i][j] = B' (A_j ... A_{i+1})' P~_{j+1} B  (i <= j), + R on the diagonal blocks,
 //                  one column per lane: L = P~_{j+1} B e_c, then L <- A_{i+1}' L down the steps.
+// The first three are not run as recursions (dense_condense).  Every A_m is I + N_m with N_m = dt blkdiag(Rz_m, I)
+// from the velocities to the positions and N_j N_k = 0, so A_{n-1} ... A_m = I + N_m + ... + N_{n-1}: c_m, mu_m and
+// the columns 6-11 of P~_m are sums over the steps of terms in cos / sin psi_j.  Lane l < H holds step l, and the
+// sums are prefix / suffix scans of DPP row 0 (H <= 16).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -123,24 +127,48 @@ struct DSmem {
     ldouble* tf;    // 36: terrain frames R_j (row-major)
     ldouble* cs;    // 2H
     ldouble* xr;    // 12H
-    ldouble* em;    // 12H: Q (c_{m+1} - xref_m)
     ldouble* Ht;    // 10 tiles: upper tiles of H
     ldouble* gv;    // 64: condensed gradient
     ldouble* vec;   // 64: right-hand side in / solution out
     ldouble* vec2;  // 64: matvec operand / result
     ldouble* blk;   // 180: per-leg-step 3x3 block (D in the IPM, T in the polish)
-    ldouble* act;   // 20: 1 = leg-step coupled (T != 0)
     ldouble* lup;   // 60: polish particular solution up per leg-step (kept out of registers)
     ldouble* lua;   // 64: predictor step u_aff per leg-step (interior point) | the last factorised polish round's
                     //     solution y0 by variable (polish, range-space rounds: lmpc_dense_kernel.h)
     ldouble* lhg;   // 64: H up + g of the last factorised polish round (range-space rounds' new directions)
-    ldouble* scr;   // union: P~ columns 6-11 (72H) during condensation | diag_inverse: T, W staging (256) W' (272) | h_matvec (48)
+    ldouble* scr;   // union: condensation: mu by step (96), P~ sums by step (85), the H columns' store sinks (DN_SINK..)
+                    //        | diag_inverse: T, W staging (256) W' (272) | h_matvec (48)
                     //        | range-space rounds: h_matvec (48), entries (48..120), solves and column vectors (128..512)
     lint* lsm;      // 20: stance leg-step b -> 4k + j
     lint* fb;       // H+1: first stance leg-step of step k
 };
 constexpr int DN_EL = 16 * 17;               // staging of one 16x16 tile, column stride 17
 constexpr int DN_SCR_MIN = 256 + DN_EL;  // diag_inverse: staging of T and W (128 each) | W'
+// condensation's sinks: lane l's predicated-off H stores go to DN_SINK + l + {0, 1, 2, 16, 32}, past the step sums
+constexpr int DN_SINK = 192;
+static_assert(6 * DENSE_MAX_H + 5 * (DENSE_MAX_H + 1) <= DN_SINK && DN_SINK + 63 + 32 < DN_SCR_MIN, "condensation scratch");
+
+typedef double __attribute__((ext_vector_type(2))) dpair;
+typedef __attribute__((address_space(3))) dpair lpair;
+
+// DPP row shifts by 1, 2, 4, 8 lanes; a lane whose source lies outside its 16-lane row reads 0 (dpp_f64's bound_ctrl)
+constexpr int DPP_ROW_SHL1 = 0x101, DPP_ROW_SHL2 = 0x102, DPP_ROW_SHL4 = 0x104, DPP_ROW_SHL8 = 0x108;  // from lane + n
+constexpr int DPP_ROW_SHR1 = 0x111, DPP_ROW_SHR2 = 0x112, DPP_ROW_SHR4 = 0x114, DPP_ROW_SHR8 = 0x118;  // from lane - n
+// inclusive scans over a 16-lane row: row_prefix sums the lanes up to this one, row_suffix those from this one on
+__device__ __forceinline__ double row_prefix(double v) {
+    v += dpp_f64<DPP_ROW_SHR1>(v);
+    v += dpp_f64<DPP_ROW_SHR2>(v);
+    v += dpp_f64<DPP_ROW_SHR4>(v);
+    v += dpp_f64<DPP_ROW_SHR8>(v);
+    return v;
+}
+__device__ __forceinline__ double row_suffix(double v) {
+    v += dpp_f64<DPP_ROW_SHL1>(v);
+    v += dpp_f64<DPP_ROW_SHL2>(v);
+    v += dpp_f64<DPP_ROW_SHL4>(v);
+    v += dpp_f64<DPP_ROW_SHL8>(v);
+    return v;
+}
 
 __device__ __forceinline__ DSmem dcarve(double* sm, int H) {
     DSmem s;
@@ -154,14 +182,12 @@ __device__ __forceinline__ DSmem dcarve(double* sm, int H) {
     s.vec = p; p += 64;
     s.vec2 = p; p += 64;
     s.blk = p; p += 180;
-    s.act = p; p += 20;
     s.lup = p; p += 60;
     s.lua = p; p += 64;
     s.cs = p; p += 2 * H;
     s.xr = p; p += 12 * H;
-    s.em = p; p += 12 * H;
     s.lhg = p; p += 64;
-    s.scr = p; p += (72 * H > DN_SCR_MIN ? 72 * H : DN_SCR_MIN);
+    s.scr = p; p += DN_SCR_MIN;
     lint* ip = (lint*)p;
     s.lsm = ip;
     s.fb = ip + 20;
@@ -169,7 +195,8 @@ __device__ __forceinline__ DSmem dcarve(double* sm, int H) {
 }
 
 // ---------------------------------------------------------------------------
-// Condensation: em, g, P~, H (see the header comment).  All lanes; lane v = variable v.
+// Condensation: g and H (see the header comment).  Lane l < H = step l for the sums over the steps, then
+// lane v = variable v.
 // ---------------------------------------------------------------------------
 #ifdef LMPC_STAMPS
 // Diagnostic build only: cycles of the condensation's sub-phases per QP (tools/dense_check.py stamps).
@@ -183,34 +210,44 @@ __device__ unsigned long long lmpc_condense_stamps[4096][5];
 #endif
 // The H-column pass keeps G0's rows 0-2 in registers on flat ground (round 5: H columns 21.3 k -> 17.1 k cycles per
 // QP, config 2 -0.7 % against LDS loads in the loop, profiles/r05/border/ab_hoist_g0.log).  Loading the step's yaw
-// terms one iteration ahead here and in the free response changed neither phase's cycles and was not kept.
+// terms one iteration ahead there did not change its cycles and was not kept.  The sums over the steps and the
+// hoisted store bookkeeping: condensation 31.9 k -> 15.2 k cycles per QP (profiles/condense/).
 template <bool TERRAIN>
 __device__ __forceinline__ void dense_condense(const DevParams& prm, const DSmem& S, int H, int nls,
                                                unsigned long long smask, int lane) {
     const double dt = prm.dt;
     CSTAMP_DECL
-    // ---- free response and adjoint (every lane redundantly: no exchange needed) ----
+    // ---- step lanes: lane l < H holds step l's yaw terms; every sum over the steps is a scan of DPP row 0 ----
+    const bool sl = lane < H;
+    const int ls = sl ? lane : 0;
+    const double ckl = S.cs[2 * ls], skl = S.cs[2 * ls + 1];
+    const double ck = sl ? ckl : 0.0, sk = sl ? skl : 0.0;
+    // free response: e = Q (c_{l+1} - xref_l) from C, Sn = sums of cos / sin psi over the steps 0..l
+    double e[12];
     {
-        double x[12];
+        double x[12], xr[12];
 #pragma unroll
-        for (int r = 0; r < 12; ++r) x[r] = S.hdr[r];
-        for (int m = 0; m < H; ++m) {
-            const double ck = S.cs[2 * m], sk = S.cs[2 * m + 1];
-            const double x6 = x[6], x7 = x[7], x8 = x[8];
-            x[0] += dt * (ck * x6 + sk * x7);
-            x[1] += dt * (-sk * x6 + ck * x7);
-            x[2] += dt * x8;
-            x[3] += dt * x[9];
-            x[4] += dt * x[10];
-            x[5] += dt * x[11];
-            x[11] -= prm.grav * dt;
-            if (lane < 12) {
-                double xl = x[0];
-#pragma unroll
-                for (int r = 1; r < 12; ++r) xl = (lane == r) ? x[r] : xl;
-                S.em[12 * m + lane] = prm.q[lane] * (xl - S.xr[12 * m + lane]);
-            }
+        for (int r = 0; r < 12; ++r) {
+            x[r] = S.hdr[r];
+            xr[r] = S.xr[12 * ls + r];
         }
+        const double C = row_prefix(ck), Sn = row_prefix(sk);
+        const double n = (double)(lane + 1), gd = prm.grav * dt;
+        double c[12];
+        c[0] = x[0] + dt * (C * x[6] + Sn * x[7]);
+        c[1] = x[1] + dt * (C * x[7] - Sn * x[6]);
+        c[2] = x[2] + dt * (n * x[8]);
+        c[3] = x[3] + dt * (n * x[9]);
+        c[4] = x[4] + dt * (n * x[10]);
+        c[5] = x[5] + dt * (n * x[11] - gd * (0.5 * n * (n - 1.0)));  // v_z falls after p_z has used it
+        c[6] = x[6];
+        c[7] = x[7];
+        c[8] = x[8];
+        c[9] = x[9];
+        c[10] = x[10];
+        c[11] = x[11] - n * gd;
+#pragma unroll
+        for (int r = 0; r < 12; ++r) e[r] = sl ? prm.q[r] * (c[r] - xr[r]) : 0.0;
     }
     CSTAMP(0);  // free response
     // variable of this lane
@@ -232,90 +269,73 @@ __device__ __forceinline__ void dense_condense(const DevParams& prm, const DSmem
     for (int q = 0; q < 6; ++q) gc[q] = S.G0[q * 12 + vc];
 #pragma unroll
     for (int ap = 0; ap < 3; ++ap) rbl[ap] = S.rb[6 * vj + sym3(ap, va)];
+    // adjoint: lane l gets mu_{l+1}.  Rows 0-5 are the suffix sums E of e; rows 6-11 the suffix sums of
+    // e[6:12] + N_{l+1}' E_{l+2}, whose second term lane l + 1 forms from its own yaw terms and E.
     {
-        double mu[12];
+        double E[6], mu[6];
 #pragma unroll
-        for (int r = 0; r < 12; ++r) mu[r] = 0.0;
-        double gval = 0.0;
-        for (int m = H; m >= 1; --m) {
-            if (m < H) {  // mu <- A_m' mu
-                const double ck = S.cs[2 * m], sk = S.cs[2 * m + 1];
-                const double m0 = mu[0], m1 = mu[1], m2 = mu[2];
-                mu[6] += dt * (ck * m0 - sk * m1);
-                mu[7] += dt * (sk * m0 + ck * m1);
-                mu[8] += dt * m2;
-                mu[9] += dt * mu[3];
-                mu[10] += dt * mu[4];
-                mu[11] += dt * mu[5];
-            }
+        for (int r = 0; r < 6; ++r) E[r] = row_suffix(e[r]);
+        double t[6];
+        t[0] = dt * (ck * E[0] - sk * E[1]);
+        t[1] = dt * (sk * E[0] + ck * E[1]);
+        t[2] = dt * E[2];
+        t[3] = dt * E[3];
+        t[4] = dt * E[4];
+        t[5] = dt * E[5];
 #pragma unroll
-            for (int r = 0; r < 12; ++r) mu[r] += S.em[12 * (m - 1) + r];
-            if (vvalid && vk + 1 == m) {
-                double gs = 0.0;
+        for (int q = 0; q < 6; ++q) mu[q] = row_suffix(e[6 + q] + dpp_f64<DPP_ROW_SHL1>(t[q]));
+        if (lane < DENSE_MAX_H) {
 #pragma unroll
-                for (int q = 0; q < 6; ++q) gs += gc[q] * mu[6 + q];
-                gval = gs;
-            }
-        }
-        S.gv[lane] = gval;
-    }
-    CSTAMP(1);  // adjoint + gradient
-    // ---- P~ recursion on the matrix cores; store P~_m[:, 6:12] for m = 1..H ----
-    {
-        const int lc = lane & 15, lr = lane >> 4;
-        d4 P;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int r = lr + 4 * i;
-            P[i] = (r == lc && r < 12) ? prm.q[r < 12 ? r : 0] : 0.0;
-        }
-        const d4 Qd = P;
-        double nc[2], ns[2], n1[2];
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            const int r = 4 * kk + lr, c = lc;
-            nc[kk] = ns[kk] = n1[kk] = 0.0;
-            if (r < 3 && c >= 6 && c < 9) {
-                const int j = c - 6;
-                if (r == 0) { nc[kk] = (j == 0) ? dt : 0.0; ns[kk] = (j == 1) ? dt : 0.0; }
-                if (r == 1) { ns[kk] = (j == 0) ? -dt : 0.0; nc[kk] = (j == 1) ? dt : 0.0; }
-                if (r == 2) n1[kk] = (j == 2) ? dt : 0.0;
-            }
-            if (r >= 3 && r < 6 && c == r + 6) n1[kk] = dt;
-        }
-        for (int m = H; m >= 1; --m) {
-            if (m < H) {
-                const double ck = S.cs[2 * m], sk = S.cs[2 * m + 1];
-                double nh[2];
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) nh[kk] = fma(nc[kk], ck, fma(ns[kk], sk, n1[kk]));
-                d4 PA = P;
-                PA = MFMA64(P[0], nh[0], PA);
-                PA = MFMA64(P[1], nh[1], PA);
-                d4 Pn = Qd + PA;
-                Pn = MFMA64(nh[0], PA[0], Pn);
-                Pn = MFMA64(nh[1], PA[1], Pn);
-                P = Pn;
-            }
-            if (lc >= 6 && lc < 12) {
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    const int r = lr + 4 * i;
-                    S.scr[72 * (m - 1) + 6 * r + (lc - 6)] = P[i];
-                }
-            }
+            for (int q = 0; q < 6; ++q) S.scr[6 * lane + q] = mu[q];
         }
     }
-    CSTAMP(2);  // P~ recursion
+    CSTAMP(1);  // adjoint
+    // ---- cost-to-go without its recursion ----
+    // P~_m[:, 6:12] is block diagonal by axis.  Its z and linear entries are polynomials in H - m (taken where the
+    // columns start below); the yaw-coupled x, y part of lane l's P~_l is, with rho_j = H - j,
+    //   rows 0-1:  dt diag(q0, q1) [uc us; -us uc],  (uc, us) = sum_{j >= l} rho_j (cos, sin) psi_j
+    //   rows 6-7:  (H - l + 1) diag(q6, q7) + dt^2 [sa sb; sb sd], the sums over j >= l of step j's
+    //              rho_j Rz_j' diag(q0, q1) Rz_j + Rz_j' diag(q0, q1) U_{j+1} + its transpose.
+    {
+        const double rho = (double)(H - lane), q0 = prm.q[0], q1 = prm.q[1];
+        const double uc = row_suffix(rho * ck), us = row_suffix(rho * sk);
+        const double un = dpp_f64<DPP_ROW_SHL1>(uc), vn = dpp_f64<DPP_ROW_SHL1>(us);  // U_{l+1}
+        const double hc = fma(rho, ck, un + un), hs = fma(rho, sk, vn + vn);
+        const double da = q0 * (ck * hc) + q1 * (sk * hs);
+        const double dd = q0 * (sk * hs) + q1 * (ck * hc);
+        const double db = (q0 - q1) * fma(ck, fma(rho, sk, vn), sk * un);
+        const double sa = row_suffix(da), sb = row_suffix(db), sd = row_suffix(dd);
+        if (lane <= DENSE_MAX_H) {  // lane H (all zero: P~_H = Q) included
+            ldouble* ps = S.scr + 6 * DENSE_MAX_H + 5 * lane;
+            ps[0] = uc;
+            ps[1] = us;
+            ps[2] = sa;
+            ps[3] = sb;
+            ps[4] = sd;
+        }
+    }
+    CSTAMP(2);  // P~ sums
     // ---- H: zero tiles, identity on padding / unused slots, then one column per lane ----
-#pragma unroll 4
-    for (int e = lane; e < 10 * DN_TILE; e += 64) S.Ht[e] = 0.0;
+    {
+        lpair* Hz = (lpair*)S.Ht;  // 16-byte stores (the carve keeps Ht 16-byte aligned)
+        const dpair zero = {0.0, 0.0};
+#pragma unroll
+        for (int q = 0; q < 10 * DN_TILE / 128; ++q) Hz[64 * q + lane] = zero;
+    }
     LMPC_SYNC();
     {
         // identity on the diagonal of padding and unused variables (lane v = variable v)
         if (!vvalid) S.Ht[tix(vt, vt) * DN_TILE + toff(vw, vw)] = 1.0;
     }
-    CSTAMP(3);  // H zero + identity
+    {
+        // gradient g_v = (B e_v)' mu_{vk+1}, from the step lanes' mu
+        const ldouble* mu = S.scr + 6 * vk;
+        double gs = 0.0;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) gs += gc[q] * mu[q];
+        S.gv[lane] = vvalid ? gs : 0.0;
+    }
+    CSTAMP(3);  // H zero + identity, gradient
     {
         // Column v of H (this lane's variable: leg-step vb at step vk, leg vj, component va):
         //   L_i = (A_vk ... A_{i+1})' P~_{vk+1} B e_v for i = vk..0, and H[v'][v] = G0_j'^T L_i[6:12] for the stance
@@ -323,18 +343,44 @@ __device__ __forceinline__ void dense_condense(const DevParams& prm, const DSmem
         //   the stance legs of step i come from the ballot (smask: bit 4k+j) in scalar registers, so no LDS load
         //   (first leg-step of the step, leg of the leg-step) sits ahead of the G0 loads.
         const double dtm = dt / prm.mass;
+        const int vkk = vvalid ? vk : -1;  // padding / unused lanes take part in no step
+        // Where this lane's stores go, fixed before the loop.  Leg-step bp's three values land in rows 3 (bp % 5)..
+        // of tile (bp / 5, vt), a uniform offset on the lane's column pointer; the lane owns them for bp <= lastb
+        // (through the last leg-step of its own step, inside its tile row) and mirrors them into its diagonal tile
+        // for the mlen leg-steps from mlo on (its tile's leg-steps of earlier steps).  Any other lane stores to a
+        // sink word of its own in the scratch: one address select per group of stores, no exec toggling.
+        ldouble* const sink = S.scr + DN_SINK + lane;
+        ldouble* const dcol = S.Ht + vt * DN_TILE + vw;
+        ldouble* const mrow = S.Ht + tix(vt, vt) * DN_TILE + 16 * vw;
+        const int mlo = 5 * vt;
+        int lastb = -1, mlen = 0;
+        if (vvalid) {
+            const int f0 = S.fb[vk], f1 = S.fb[vk + 1];
+            lastb = min(f1 - 1, mlo + 4);
+            mlen = max(f0 - mlo, 0);
+        }
+        // L = P~_{k+1} B e_v from the sums of the step lanes (k = vk, r = H - 1 - k steps follow step k + 1)
         double L[12];
         {
-            const ldouble* Pt = S.scr + 72 * vk;  // P~_{k+1}
+            const ldouble* ps = S.scr + 6 * DENSE_MAX_H + 5 * (vk + 1);
+            const double uc = ps[0], us = ps[1], sa = ps[2], sb = ps[3], sd = ps[4];
+            const int r = H - 1 - vk;
+            const double cnt = (double)(r + 1);
+            const double w1 = (double)(r * (r + 1) / 2);                // sum of n, n = 0..r
+            const double w2 = (double)(r * (r + 1) * (2 * r + 1) / 6);  // sum of n^2
+            const double dt2 = dt * dt;
+            L[0] = dt * prm.q[0] * (uc * gc[0] + us * gc[1]);
+            L[1] = dt * prm.q[1] * (uc * gc[1] - us * gc[0]);
+            L[6] = fma(cnt, prm.q[6] * gc[0], dt2 * (sa * gc[0] + sb * gc[1]));
+            L[7] = fma(cnt, prm.q[7] * gc[1], dt2 * (sb * gc[0] + sd * gc[1]));
+            L[2] = dt * prm.q[2] * w1 * gc[2];
+            L[8] = fma(cnt, prm.q[8], dt2 * prm.q[2] * w2) * gc[2];
 #pragma unroll
-            for (int r = 0; r < 12; ++r) {
-                double acc = 0.0;
-#pragma unroll
-                for (int q = 0; q < 6; ++q) acc = fma(Pt[6 * r + q], gc[q], acc);
-                L[r] = acc;
+            for (int a = 0; a < 3; ++a) {
+                L[3 + a] = dt * prm.q[3 + a] * w1 * gc[3 + a];
+                L[9 + a] = fma(cnt, prm.q[9 + a], dt2 * prm.q[3 + a] * w2) * gc[3 + a];
             }
         }
-        const int vkk = vvalid ? vk : -1;  // padding / unused lanes take part in no step
         // flat ground: rows 0-2 of G0 in registers (loop-invariant; in the loop they are LDS loads the compiler cannot
         // hoist past the H stores, which may alias)
         double g0r[3][12];
@@ -356,33 +402,50 @@ __device__ __forceinline__ void dense_condense(const DevParams& prm, const DSmem
                 L[11] += dt * L[5];
             }
             const unsigned legs = (unsigned)(smask >> (4 * i)) & 15u;
-            int bp = __popcll(smask & ((1ull << (4 * i)) - 1ull));  // first stance leg-step of step i
+            if (!legs) continue;  // uniform
+            // first stance leg-step of step i, its tile row and slot: counted on from here, no division per leg-step
+            int bp = __popcll(smask & ((1ull << (4 * i)) - 1ull));
+            int tp = (bp * 13) >> 6, sp = bp - 5 * tp;  // bp / 5 for bp < 64
 #pragma unroll
             for (int jp = 0; jp < 4; ++jp) {
                 if (!((legs >> jp) & 1u)) continue;  // uniform
-                if (i <= vkk) {
-                    const int vb0 = 16 * (bp / 5) + 3 * (bp % 5);  // first variable of leg-step bp
-                    const int tp = vb0 >> 4;
+                double val[3];
 #pragma unroll
-                    for (int ap = 0; ap < 3; ++ap) {
-                        const int cp = 3 * jp + ap;
-                        double val = 0.0;
-                        if constexpr (TERRAIN) {
+                for (int ap = 0; ap < 3; ++ap) {
+                    const int cp = 3 * jp + ap;
+                    double v = 0.0;
+                    if constexpr (TERRAIN) {
 #pragma unroll
-                            for (int q = 0; q < 6; ++q) val = fma(S.G0[q * 12 + cp], L[6 + q], val);
-                        } else {  // flat ground: rows 3-5 of G0 are dt/m I (dense_prologue) -- the same sum, bit for bit
+                        for (int q = 0; q < 6; ++q) v = fma(S.G0[q * 12 + cp], L[6 + q], v);
+                    } else {  // flat ground: rows 3-5 of G0 are dt/m I (dense_prologue) -- the same sum, bit for bit
 #pragma unroll
-                            for (int q = 0; q < 3; ++q) val = fma(g0r[q][cp], L[6 + q], val);
-                            val = fma(dtm, L[9 + ap], val);
-                        }
-                        if (bp == vb) val += rbl[ap];
-                        const int vp = vb0 + ap;
-                        if (tp <= vt) S.Ht[tix(tp, vt) * DN_TILE + toff(vp & 15, vw)] = val;
-                        if (tp == vt && i < vkk) S.Ht[tix(vt, vt) * DN_TILE + toff(vw, vp & 15)] = val;
+                        for (int q = 0; q < 3; ++q) v = fma(g0r[q][cp], L[6 + q], v);
+                        v = fma(dtm, L[9 + ap], v);
                     }
+                    val[ap] = v;
                 }
+                // tiles (tp, vt) start 256 (3 tp - tp (tp - 1) / 2) doubles past tile (0, vt): 0, 3, 5, 6 tiles
+                const int trow = (int)((0x0600050003000000ull >> (16 * tp)) & 0xffffull);
+                ldouble* const pd = bp <= lastb ? dcol + (trow + 48 * sp) : sink;
+                pd[0] = val[0];
+                pd[16] = val[1];
+                pd[32] = val[2];
+                ldouble* const pm = (unsigned)(bp - mlo) < (unsigned)mlen ? mrow + 3 * sp : sink;
+                pm[0] = val[0];
+                pm[1] = val[1];
+                pm[2] = val[2];
                 ++bp;
+                if (++sp == 5) {
+                    sp = 0;
+                    ++tp;
+                }
             }
+        }
+        // + R on the lane's own 3x3 block (rows vw - va.. of its column in the diagonal tile), once after the loop
+        if (vvalid) {
+            ldouble* const pr = mrow + (vw - 16 * va);  // element (vw - va, vw)
+#pragma unroll
+            for (int ap = 0; ap < 3; ++ap) pr[16 * ap] += rbl[ap];
         }
     }
     LMPC_SYNC();
@@ -495,17 +558,14 @@ static __device__ __attribute__((always_inline)) DiagInv diag_inverse(ldouble* s
 }
 
 
-// coupled-block mask of tile t (bits 0-4: leg-steps 5t..5t+4 valid, and with use_act also coupled)
-__device__ __forceinline__ int tile_mask(const DSmem& S, int t, int nls, bool use_act) {
-    int m = 0;
-#pragma unroll
-    for (int s = 0; s < 5; ++s) {
-        const int b = 5 * t + s;
-        const double a = S.act[b < 20 ? b : 0];  // loaded unconditionally: no branch waits on it
-        m |= ((b < nls) & (!use_act | (a != 0.0))) << s;
-    }
-    return __builtin_amdgcn_readfirstlane(m);
+// Coupled-block masks of a factorisation's four tiles, computed once ahead of the tile loop: bit b = leg-step b is
+// valid (b < nls) and coupled (bit b of `coupled`: all ones in the interior point and the dual active set, the
+// ballot of T != 0 in a polish round).  Scalar: nothing is loaded or waited on between the tiles.
+__device__ __forceinline__ unsigned tile_masks(int nls, unsigned coupled) {
+    return __builtin_amdgcn_readfirstlane(((1u << nls) - 1u) & coupled);  // nls <= DENSE_MAX_LS = 20
 }
+// mask of tile t (bits 0-4: leg-steps 5t..5t+4)
+__device__ __forceinline__ int tile_mask(unsigned masks, int t) { return (int)((masks >> (5 * t)) & 31u); }
 
 // lane-wise y = H x for the variables (lane v = variable v; x in LDS by variable), H from its upper tiles in LDS,
 // as VALU tile products in the accumulator layout (lane 16g + c, register i <-> tile element (4i + g, c)):
@@ -560,18 +620,37 @@ __device__ __forceinline__ double h_matvec(const DSmem& S, const ldouble* x, ldo
 // yaw cos/sin of every step, per-leg input Hessian blocks.  smask = ballot of stance leg-steps
 // (lane 4k + j).  Returns this lane's rank among the stance leg-steps (valid when stl).
 // ---------------------------------------------------------------------------
+// The QP's record (33 + 12 H <= 4 x 64 doubles) in flight: lane l's elements l, l + 64, ...  Issued right after the
+// contact bytes' load and ahead of the wait on them -- its address does not depend on the contacts, so the two global
+// round trips at the head of the QP overlap.  A QP that leaves for the Riccati body drops the values.
+struct DenseRec {
+    double v[4];
+};
+static_assert(33 + 12 * DENSE_MAX_H <= 4 * 64, "DenseRec holds a whole record");
+__device__ __forceinline__ DenseRec dense_rec_load(const double* __restrict__ rec, int qp, int H, int lane) {
+    const int RL = 33 + 12 * H;
+    const double* rin = rec + (size_t)qp * RL;
+    DenseRec r;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int i = lane + 64 * q;
+        r.v[q] = rin[i < RL ? i : 0];
+    }
+    return r;
+}
+
 template <bool TERRAIN>
-__device__ __forceinline__ int dense_prologue(const DevParams& prm, const DSmem& S, const double* __restrict__ rec,
+__device__ __forceinline__ int dense_prologue(const DevParams& prm, const DSmem& S, const DenseRec& rv,
                                               const double* __restrict__ normals, int qp, int H,
                                               unsigned long long smask, bool stl, int lane) {
     const int RL = 33 + 12 * H;
     const double dt = prm.dt;
     // ---- record, leg-step map ----
-    const double* rin = rec + (size_t)qp * RL;
-    for (int i = lane; i < RL; i += 64) {
-        const double v = rin[i];
-        if (i < 33) S.hdr[i] = v;
-        else S.xr[i - 33] = v;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int i = lane + 64 * q;
+        if (i < 33) S.hdr[i] = rv.v[q];
+        else if (i < RL) S.xr[i - 33] = rv.v[q];
     }
     const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(smask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)smask, 0));
     if (stl) S.lsm[rank] = lane;

@@ -117,7 +117,9 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
     const int lane = threadIdx.x;
     const int H = prm.H;
     // ---- stance leg-steps: ballot over lane i = 4k + j ----
-    const bool stl = lane < 4 * H && contact[(size_t)qp * 4 * H + lane] != 0;
+    const uint8_t cbyte = contact[(size_t)qp * 4 * H + (lane < 4 * H ? lane : 0)];
+    const DenseRec rv = dense_rec_load(rec, qp, H, lane);  // in flight while the contact bytes are waited on
+    const bool stl = lane < 4 * H && cbyte != 0;
     const unsigned long long smask = __ballot(stl);
     const int nls = __popcll(smask);
     if (nls > DENSE_MAX_LS || nls == 0) return false;  // Riccati kernel (it also owns the all-swing QPs)
@@ -125,7 +127,7 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
     const double mu = prm.mu, fzmax = prm.fmax, dt = prm.dt;
     DSTAMP_DECL
 
-    const int rank = dense_prologue<TERRAIN>(prm, S, rec, normals, qp, H, smask, stl, lane);
+    const int rank = dense_prologue<TERRAIN>(prm, S, rv, normals, qp, H, smask, stl, lane);
     DSTAMP(0);  // prologue
     dense_condense<TERRAIN>(prm, S, H, nls, smask, lane);
     // Always four tiles: leg-steps beyond nls are identity padding (exact, and it keeps every tile
@@ -167,6 +169,8 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
     // polish rounds after a polish round: diagonal tiles before the first leg-step whose active set changed keep their
     // factors (their M tiles, and every panel and update feeding them, are bitwise those of the previous round)
     int keep_tiles = 0;
+    // coupled leg-steps (T != 0) of the current factorised polish round: bit b = leg-step b (uniform)
+    unsigned cmask = 0;
     bool apex = false;
     // Range-space polish rounds (LMPC_POLISH_SCHUR): a round whose active set only adds faces to the set of the last
     // factorised round (bact, per leg-step lane) is that round's equality QP with k more rows A y = d on its
@@ -356,6 +360,7 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
         if (mode == POLISH && !schur) {
             S.vec2[lane] = 0.0;  // padding / unused variables of the up vector
             LMPC_SYNC();
+            bool coupled = false;
             if (st) {
                 const double (&T)[9] = Tn;
                 const double (&up)[3] = upn;
@@ -364,13 +369,12 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
                 ldouble* bk = S.blk + 9 * lane;
 #pragma unroll
                 for (int e = 0; e < 9; ++e) bk[e] = T[e];
-                bool coupled = false;
 #pragma unroll
                 for (int e = 0; e < 9; ++e) coupled |= T[e] != 0.0;
-                S.act[lane] = coupled ? 1.0 : 0.0;
 #pragma unroll
                 for (int p = 0; p < 3; ++p) S.vec2[vidx(lane, p)] = up[p];
             }
+            cmask = (unsigned)__ballot(coupled);
         }
         // ---- right-hand side (and, except in the corrector, the Newton matrix) ----
         if (schur) {
@@ -464,12 +468,15 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
             if (mode == POLISH) DSTAMP(7);  // M tiles (polish)
             else DSTAMP(3);                  // M tiles (interior point)
             // ---- tiled Cholesky M = U'U ----
+            // the four tiles' coupled-block masks at once (tile_masks): from nls alone in the interior point, and with
+            // the round's coupled leg-steps in the polish -- scalar work, nothing loaded between the tiles
+            const unsigned tmasks = tile_masks(nls, mode == POLISH ? cmask : ~0u);
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
                 if (b >= NT) continue;
                 DSTAMP(4);
                 if (b >= keep_tiles) {
-                    const DiagInv di = diag_inverse(S.scr, Tl[tix(b, b)], tile_mask(S, b, nls, mode == POLISH), lane);
+                    const DiagInv di = diag_inverse(S.scr, Tl[tix(b, b)], tile_mask(tmasks, b), lane);
                     Ui[b] = di.ui;
                     UiT[b] = di.uit;
                 }

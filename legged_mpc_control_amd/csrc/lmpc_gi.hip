@@ -208,7 +208,9 @@ __global__ void __launch_bounds__(64) lmpc_gi_kernel(const DevParams prm, const 
     if (qp >= batch) return;
     const int lane = threadIdx.x;
     const int H = prm.H;
-    const bool stl = lane < 4 * H && contact[(size_t)qp * 4 * H + lane] != 0;
+    const uint8_t cbyte = contact[(size_t)qp * 4 * H + (lane < 4 * H ? lane : 0)];
+    const DenseRec rv = dense_rec_load(rec, qp, H, lane);  // in flight while the contact bytes are waited on
+    const bool stl = lane < 4 * H && cbyte != 0;
     const unsigned long long smask = __ballot(stl);
     const int nls = __popcll(smask);
     if (nls > DENSE_MAX_LS || nls == 0) return;  // Riccati kernel (it also owns the all-swing QPs)
@@ -217,7 +219,7 @@ __global__ void __launch_bounds__(64) lmpc_gi_kernel(const DevParams prm, const 
     const double mu = prm.mu, fzmax = prm.fmax;
     GSTAMP_DECL
 
-    const int rank = dense_prologue<TERRAIN>(prm, S, rec, normals, qp, H, smask, stl, lane);
+    const int rank = dense_prologue<TERRAIN>(prm, S, rv, normals, qp, H, smask, stl, lane);
     dense_condense<TERRAIN>(prm, S, H, nls, smask, lane);
     GSTAMP(0);  // prologue + condensation
 
@@ -236,7 +238,7 @@ __global__ void __launch_bounds__(64) lmpc_gi_kernel(const DevParams prm, const 
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
             {
-                const DiagInv di = diag_inverse(S.scr, Tl[tix(b, b)], tile_mask(S, b, nls, false), lane);
+                const DiagInv di = diag_inverse(S.scr, Tl[tix(b, b)], tile_mask(tile_masks(nls, ~0u), b), lane);
                 Ui[b] = di.ui;
                 UiT[b] = di.uit;
             }

@@ -81,16 +81,16 @@ def stamps():
         v = buf[:n, i].astype(float).mean()
         print(f"  {nm:20s} {v:10.0f} ({100 * v / tot.mean():5.1f}%)")
     print(f"  max cycles/QP {tot.max():.0f}, p99 {np.percentile(tot, 99):.0f}")
-    if os.environ.get("LMPC_STAMPS_OUT"):  # per-QP phase cycles and iteration words, for comparing builds
-        np.savez(os.environ["LMPC_STAMPS_OUT"], stamps=buf[:n], iters=it[:n])
     for q in np.argsort(-tot)[:6]:
         print(f"    slow QP {q}: {tot[q]:.0f} cycles, ipm {it[q] & 0xffff} rounds {it[q] >> 16}, "
               f"diag {buf[q, 6]:.0f} solve {buf[q, 5]:.0f}")
     L.lmpc_debug_condense_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int]
     cb = np.zeros((1024, 5), dtype=np.uint64)
     n = L.lmpc_debug_condense_stamps(cb.ctypes.data, 1024)
-    for i, nm in enumerate(["free response", "adjoint + gradient", "P~ recursion", "H zero + identity", "H columns"]):
+    for i, nm in enumerate(["free response", "adjoint", "P~ sums", "H zero + identity + g", "H columns"]):
         print(f"    condense: {nm:20s} {cb[:n, i].astype(float).mean():10.0f}")
+    if os.environ.get("LMPC_STAMPS_OUT"):  # per-QP phase cycles and iteration words, for comparing builds
+        np.savez(os.environ["LMPC_STAMPS_OUT"], stamps=buf[:n], condense=cb[:n], iters=it[:n])
     return tot
 
 

@@ -8,12 +8,13 @@ include/lmpc/lmpc.h.
 from . import _native
 from ._native import (GAIT_CRAWL, GAIT_STAND, GAIT_TROT, GAIT_TROT_WITH_STAND, LmpcCommand, LmpcLegKin,
                       LmpcOptions, LmpcParams, LmpcRbdModel, LmpcRbdState, LmpcRbdTerms, LmpcRobot, LmpcRolloutCfg,
-                      LmpcRolloutLog, LmpcSimCfg, LmpcSimOut, LmpcWbcTarget, NativeLibraryError)
+                      LmpcRolloutLog, LmpcSimCfg, LmpcSimOut, LmpcStackRobot, LmpcWbcTarget, NativeLibraryError)
 from .solver import (BatchedConvexQPSolver, ConvexQPSolver, LeggedContactFSM, LeggedCtrl, LeggedFeedback,
                      LeggedParam, LeggedState, foot_jacobian, grf_to_torque, leg_kin_default, solver_options)
-from . import rbd, rollout, sim, synth
+from . import rbd, rollout, sim, stack, synth
 from .rbd import WbcPipeline
 from .sim import WbcSim
+from .stack import StackLoop
 
 __all__ = [
     "BatchedConvexQPSolver", "ConvexQPSolver", "LeggedContactFSM", "LeggedState", "LeggedFeedback",
@@ -23,4 +24,5 @@ __all__ = [
     "rollout", "LmpcRobot", "LmpcRolloutCfg", "LmpcRolloutLog",
     "rbd", "WbcPipeline", "LmpcRbdModel", "LmpcRbdState", "LmpcRbdTerms", "LmpcWbcTarget",
     "sim", "WbcSim", "LmpcSimCfg", "LmpcSimOut",
+    "stack", "StackLoop", "LmpcStackRobot",
 ]

@@ -75,6 +75,13 @@ SIM_SYMBOLS = (
     "lmpc_rbd_forward_dynamics", "lmpc_sim_step", "lmpc_rbd_forward_dynamics_device", "lmpc_sim_step_device",
 )
 SIM_ABI_VERSION = 1
+# include/lmpc/lmpc_stack.h: the full loop, MPC -> WBC -> plant
+STACK_SYMBOLS = (
+    "lmpc_stack_abi_version", "lmpc_stack_robot_size", "lmpc_stack_check_rates", "lmpc_stack_robot_init",
+    "lmpc_stack_advance", "lmpc_stack_targets", "lmpc_stack_reserve", "lmpc_stack_advance_device", "lmpc_stack_solve_device",
+    "lmpc_stack_copy_records_device", "lmpc_stack_targets_device", "lmpc_stack_candidates_device",
+)
+STACK_ABI_VERSION = 1
 
 
 class LmpcParams(ctypes.Structure):
@@ -246,6 +253,20 @@ class LmpcSimOut(ctypes.Structure):
         ("foot_vel", ctypes.c_double * 12), ("held", ctypes.c_int32 * 4), ("touch", ctypes.c_int32 * 4),
         ("status", ctypes.c_int32), ("reserved", ctypes.c_int32),
     ]
+
+
+class LmpcStackRobot(ctypes.Structure):
+    """Everything one robot's MPC carries between the ticks of the full loop (lmpc_stack_robot)."""
+    _fields_ = [
+        ("rb", LmpcRobot),
+        ("fsm_pos_target", ctypes.c_double * 12),
+        ("fsm_vel_target", ctypes.c_double * 12),
+        ("swing_end_world", ctypes.c_double * 12),
+        ("not_first_call", ctypes.c_int32 * 4),
+    ]
+
+
+STACK_ROBOT_BYTES = ctypes.sizeof(LmpcStackRobot)  # 960
 
 
 class NativeLibraryError(RuntimeError):
@@ -451,6 +472,34 @@ def lib():
         if L.lmpc_sim_abi_version() != SIM_ABI_VERSION or sim_sizes != sim_mirrors:
             raise NativeLibraryError(f"{path}: lmpc_sim.h ABI {L.lmpc_sim_abi_version()} with struct sizes {sim_sizes}, "
                                      f"this binding is ABI {SIM_ABI_VERSION} with {sim_mirrors}")
+        srp = ctypes.POINTER(LmpcStackRobot)
+        L.lmpc_stack_abi_version.restype = ctypes.c_int
+        L.lmpc_stack_robot_size.restype = ctypes.c_int
+        L.lmpc_stack_check_rates.argtypes = [pp, cfp, ctypes.c_int, ctypes.c_int]
+        L.lmpc_stack_check_rates.restype = ctypes.c_int
+        L.lmpc_stack_robot_init.argtypes = [rcp, mp, sp, dp, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                            ctypes.c_double, srp, sop]
+        L.lmpc_stack_robot_init.restype = ctypes.c_int
+        L.lmpc_stack_advance.argtypes = [pp, rcp, srp, sp, sop, dp]
+        L.lmpc_stack_advance.restype = ctypes.c_int
+        L.lmpc_stack_targets.argtypes = [srp, dp, tp, tp]
+        L.lmpc_stack_targets.restype = ctypes.c_int
+        L.lmpc_stack_reserve.argtypes = [vp, ctypes.c_int]
+        L.lmpc_stack_reserve.restype = ctypes.c_int
+        L.lmpc_stack_advance_device.argtypes = [vp, rcp, vp, vp, vp, ctypes.c_int, vp]
+        L.lmpc_stack_advance_device.restype = ctypes.c_int
+        L.lmpc_stack_solve_device.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp]
+        L.lmpc_stack_solve_device.restype = ctypes.c_int
+        L.lmpc_stack_copy_records_device.argtypes = [vp, ctypes.c_int, vp, vp, vp]
+        L.lmpc_stack_copy_records_device.restype = ctypes.c_int
+        L.lmpc_stack_targets_device.argtypes = [vp, vp, ctypes.c_int64, tp, ctypes.c_int, vp, vp]
+        L.lmpc_stack_targets_device.restype = ctypes.c_int
+        L.lmpc_stack_candidates_device.argtypes = [vp, ctypes.c_int, vp, vp]
+        L.lmpc_stack_candidates_device.restype = ctypes.c_int
+        if L.lmpc_stack_abi_version() != STACK_ABI_VERSION or L.lmpc_stack_robot_size() != STACK_ROBOT_BYTES:
+            raise NativeLibraryError(f"{path}: lmpc_stack.h ABI {L.lmpc_stack_abi_version()} / lmpc_stack_robot of "
+                                     f"{L.lmpc_stack_robot_size()} B, this binding is ABI {STACK_ABI_VERSION} / "
+                                     f"{STACK_ROBOT_BYTES} B")
         if L.lmpc_rollout_abi_version() != ROLLOUT_ABI_VERSION or L.lmpc_robot_size() != ROBOT_BYTES:
             raise NativeLibraryError(f"{path}: lmpc_rollout.h ABI {L.lmpc_rollout_abi_version()} / lmpc_robot of "
                                      f"{L.lmpc_robot_size()} B, this binding is ABI {ROLLOUT_ABI_VERSION} / {ROBOT_BYTES} B")

@@ -45,10 +45,10 @@ SCHED_FLAGS = {
     "lmpc_hoqp.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],
 }
 
-SOURCES = ["lmpc_kernels.hip", "lmpc_lq.hip", "lmpc_fused.hip", "lmpc_dense.hip", "lmpc_gi.hip", "lmpc_prep.hip", "lmpc_rollout.hip", "lmpc_hoqp.hip", "lmpc_wbc.hip", "lmpc_rbd.hip", "lmpc_sim.hip", "lmpc_capi.cpp",
+SOURCES = ["lmpc_kernels.hip", "lmpc_lq.hip", "lmpc_fused.hip", "lmpc_dense.hip", "lmpc_gi.hip", "lmpc_prep.hip", "lmpc_rollout.hip", "lmpc_hoqp.hip", "lmpc_wbc.hip", "lmpc_rbd.hip", "lmpc_sim.hip", "lmpc_stack.hip", "lmpc_capi.cpp",
            "hoqp_capi.cpp", "lmpc_host.cpp", "ConvexQPSolver.cpp"]
 HEADERS = ["lmpc_device.h", "lmpc_common.h", "lmpc_kernel_common.h", "lmpc_dense_common.h", "lmpc_dense_kernel.h", "lmpc_lq_kernel.h",
-           "lmpc_hoqp_device.h", "lmpc_rbd_common.h", "lmpc_sim_common.h"]
+           "lmpc_hoqp_device.h", "lmpc_rbd_common.h", "lmpc_sim_common.h", "lmpc_stack_common.h"]
 
 
 def hipcc() -> str:
@@ -98,7 +98,7 @@ def build_native(force: bool = False, verbose: bool = False) -> str:
     deps = srcs + [os.path.join(CSRC, h) for h in HEADERS] + [
         os.path.join(ROOT, "include", "lmpc", "lmpc.h"), os.path.join(ROOT, "include", "lmpc", "lmpc_hoqp.h"),
         os.path.join(ROOT, "include", "lmpc", "lmpc_rollout.h"), os.path.join(ROOT, "include", "lmpc", "lmpc_rbd.h"),
-        os.path.join(ROOT, "include", "lmpc", "lmpc_sim.h"),
+        os.path.join(ROOT, "include", "lmpc", "lmpc_sim.h"), os.path.join(ROOT, "include", "lmpc", "lmpc_stack.h"),
         os.path.join(ROOT, "include", "lmpc", "ConvexQPSolver.hpp"),
         os.path.abspath(__file__)]
     if not force and not _stale(LIB, deps):

@@ -13,6 +13,7 @@
 
 #include "lmpc/lmpc.h"
 #include "lmpc/lmpc_rollout.h"
+#include "lmpc/lmpc_stack.h"
 #include "lmpc_common.h"
 #include "lmpc_device.h"
 
@@ -40,6 +41,9 @@ hipError_t launch_advance(const lmpc_common::PlantParams& pp, const lmpc_rollout
                           int batch, const double* grf, int H, int book, lmpc_command* cmd_out, double* log_u0,
                           double* log_x, double* rec, uint8_t* contact, hipStream_t stream);
 hipError_t launch_shift(const uint8_t* act, int batch, int H, uint8_t* shifted, hipStream_t stream);
+hipError_t launch_stack_advance(double dt, const lmpc_rollout_cfg& cfg, lmpc_stack_robot* robots,
+                                const lmpc_rbd_state* states, const lmpc_sim_out* outs, int batch, int H, double* rec,
+                                uint8_t* contact, hipStream_t stream);
 }
 
 struct lmpc_ctx {
@@ -707,6 +711,49 @@ int lmpc_rollout_device(lmpc_ctx* c, const lmpc_rollout_cfg* cfg, lmpc_robot* d_
     }
     if (e == hipSuccess) e = ctx_leave(c, s);
     return launch_rc(e);
+}
+
+// ---- include/lmpc/lmpc_stack.h: the entry points that use the context's buffers ----
+
+int lmpc_stack_reserve(lmpc_ctx* c, int batch) {
+    if (!c || batch < 0) return LMPC_ERR_ARG;
+    DeviceScope ds(c->device);
+    if (!ds.ok) return LMPC_ERR_DEVICE;
+    if (batch > 0 && ensure_cmd(c, batch) != LMPC_OK) return LMPC_ERR_ALLOC;
+    return ensure_ws(c, batch, uses_scratch(c, c->prm));
+}
+
+int lmpc_stack_advance_device(lmpc_ctx* c, const lmpc_rollout_cfg* cfg, lmpc_stack_robot* d_robots,
+                              const lmpc_rbd_state* d_state, const lmpc_sim_out* d_sim_out, int batch, void* stream) {
+    if (!c || !cfg || batch < 0 || (batch > 0 && (!d_robots || !d_state || !d_sim_out))) return LMPC_ERR_ARG;
+    LMPC_DEVICE_ENTRY(c, s);
+    if (batch == 0) return LMPC_OK;
+    if (ensure_cmd(c, batch) != LMPC_OK) return LMPC_ERR_ALLOC;
+    // the expansion overwrites the context's record buffers: order it behind the previous solve that read them
+    hipError_t e = ctx_enter(c, s);
+    if (e == hipSuccess)
+        e = lmpc::launch_stack_advance(c->prm.dt, *cfg, d_robots, d_state, d_sim_out, batch, c->H, c->d_crec, c->d_ccon, s);
+    if (e == hipSuccess) e = ctx_leave(c, s);
+    return launch_rc(e);
+}
+
+int lmpc_stack_solve_device(lmpc_ctx* c, int batch, double* d_grf, int32_t* d_status, int32_t* d_iters, void* stream) {
+    if (!c || batch < 0 || (size_t)batch > c->cmd_qps || (batch > 0 && !d_grf)) return LMPC_ERR_ARG;
+    if (batch == 0) return LMPC_OK;
+    return lmpc_solve_batch_device_ex(c, c->d_crec, c->d_ccon, nullptr, batch, d_grf, d_status, d_iters, stream);
+}
+
+int lmpc_stack_copy_records_device(lmpc_ctx* c, int batch, double* d_rec, uint8_t* d_contact, void* stream) {
+    if (!c || batch < 0 || (size_t)batch > c->cmd_qps || (batch > 0 && (!d_rec || !d_contact))) return LMPC_ERR_ARG;
+    LMPC_DEVICE_ENTRY(c, s);
+    if (batch == 0) return LMPC_OK;
+    hipError_t e = ctx_enter(c, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d_rec, c->d_crec, (size_t)batch * lmpc_record_len(c->H) * sizeof(double),
+                           hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_contact, c->d_ccon, (size_t)batch * 4 * c->H, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = ctx_leave(c, s);
+    return e == hipSuccess ? LMPC_OK : LMPC_ERR_DEVICE;
 }
 #undef LMPC_DEVICE_ENTRY
 

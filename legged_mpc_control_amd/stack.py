@@ -1,0 +1,294 @@
+"""The full loop on the device: MPC -> whole-body controller -> rigid-body plant (include/lmpc/lmpc_stack.h).
+
+  * `robot_init()`, `advance()`, `targets()` -- one robot's MPC tick on the host (the arithmetic the device kernels
+    share): feedback from the measured state and the plant's `touch` flags, Raibert target, the leg FSMs with early
+    touchdown and their foot targets; then the WBC's targets from the QP's u_0 and those FSM targets;
+  * `advance_device()`, `solve_device()`, `targets_device()`, `candidates_device()` -- the same for a batch resident in
+    HBM, asynchronous on a stream; the advance launch also expands the commands into the MPC context's record buffers;
+  * `StackLoop` -- per MPC tick: advance, QP, targets, then `wbc_per_mpc` low-level ticks of `WbcPipeline.solve_device`
+    and `lmpc_sim_step_device`, the plant's candidate contacts being `held | touch` of its previous step; one stream,
+    no host synchronisation and no allocation inside the loop.
+
+What is restated from the reference and what is this library's choice (zero latency, the candidate rule, `touch` as
+the contact flag, the standing mode's foot targets, what a failed stage leaves): include/lmpc/lmpc_stack.h.  The
+device functions are HIP kernels; there is no CPU fallback behind them.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from . import _native as N
+from . import sim as S
+from .hoqp import check_device_tensor
+from .rbd import STATE_BYTES, TARGET_BYTES, WbcPipeline, target as wbc_target
+from .solver import BatchedConvexQPSolver
+
+ROBOT_BYTES = N.STACK_ROBOT_BYTES  # 960
+_dp = ctypes.POINTER(ctypes.c_double)
+
+STACK_ROBOT_DTYPE = np.dtype({
+    "names": ["euler", "pos", "omega", "vel", "rot", "foot_abs", "euler_d", "pos_d", "vel_d_rel", "omega_d_rel",
+              "gait_phase", "gait_speed", "gait", "plan_contacts", "foot_pos_world", "swing_start_world", "fsm_start",
+              "fsm_index", "tick", "fsm_pos_target", "fsm_vel_target", "swing_end_world", "not_first_call"],
+    "formats": ["3f8", "3f8", "3f8", "3f8", "9f8", "12f8", "3f8", "3f8", "3f8", "3f8", "4f8", "f8", "i4", "4u1",
+                "12f8", "12f8", "4f8", "4i4", "i4", "12f8", "12f8", "12f8", "4i4"],
+    "offsets": [0, 24, 48, 72, 96, 168, 264, 288, 312, 336, 360, 392, 400, 404, 408, 504, 600, 632, 648, 656, 752, 848,
+                944],
+    "itemsize": 960,
+})
+
+
+def _d(a):
+    return a.ctypes.data_as(_dp)
+
+
+def check_rates(params: N.LmpcParams, sim_cfg: N.LmpcSimCfg, wbc_per_mpc: int, substeps: int = 1) -> None:
+    """ValueError unless wbc_per_mpc * substeps * sim_cfg.dt == params.dt to 1e-12 (lmpc_stack_check_rates)."""
+    if N.lib().lmpc_stack_check_rates(ctypes.byref(params), ctypes.byref(sim_cfg), int(wbc_per_mpc), int(substeps)) != 0:
+        raise ValueError(f"wbc_per_mpc {wbc_per_mpc} x substeps {substeps} x sim dt {sim_cfg.dt} is not the MPC's dt "
+                         f"{params.dt}")
+
+
+def robot_init(cfg: N.LmpcRolloutCfg, model: N.LmpcRbdModel, state: N.LmpcRbdState, vel_d=(0.0, 0.0),
+               yaw_rate: float = 0.0, height: float = 0.30, gait: int = N.GAIT_TROT, gait_speed: float = 4.0):
+    """One robot in `state` with its FSMs at reset -> (LmpcStackRobot, the first LmpcSimOut) (lmpc_stack_robot_init)."""
+    rb, out = N.LmpcStackRobot(), N.LmpcSimOut()
+    vd = np.ascontiguousarray(vel_d, dtype=np.float64).reshape(2)
+    N.check(N.lib().lmpc_stack_robot_init(ctypes.byref(cfg), ctypes.byref(model), ctypes.byref(state), _d(vd),
+                                          float(yaw_rate), float(height), int(gait), float(gait_speed), ctypes.byref(rb),
+                                          ctypes.byref(out)), "lmpc_stack_robot_init")
+    return rb, out
+
+
+def advance(p: N.LmpcParams, cfg: N.LmpcRolloutCfg, robot: N.LmpcStackRobot, state: N.LmpcRbdState,
+            out: N.LmpcSimOut) -> np.ndarray:
+    """One robot's MPC tick before the solve, on the host, in place (lmpc_stack_advance) -> the Raibert foot targets
+    [4, 3] (world)."""
+    tgt = np.zeros(12)
+    N.check(N.lib().lmpc_stack_advance(ctypes.byref(p), ctypes.byref(cfg), ctypes.byref(robot), ctypes.byref(state),
+                                       ctypes.byref(out), _d(tgt)), "lmpc_stack_advance")
+    return tgt.reshape(4, 3)
+
+
+def targets(robot: N.LmpcStackRobot, u0, template: N.LmpcWbcTarget = None) -> N.LmpcWbcTarget:
+    """One robot's WBC targets after the solve, on the host (lmpc_stack_targets)."""
+    tmpl = template if template is not None else wbc_target()
+    u0 = np.ascontiguousarray(u0, dtype=np.float64).reshape(12)
+    t = N.LmpcWbcTarget()
+    N.check(N.lib().lmpc_stack_targets(ctypes.byref(robot), _d(u0), ctypes.byref(tmpl), ctypes.byref(t)),
+            "lmpc_stack_targets")
+    return t
+
+
+# ---- host <-> device ---------------------------------------------------------------------------------------------
+def to_bytes(structs) -> np.ndarray:
+    """A list or ctypes array of equal structs -> uint8 [B, sizeof] (a copy)."""
+    return np.stack([np.frombuffer(bytes(s), dtype=np.uint8) for s in structs])
+
+
+def robots_from(buf):
+    """uint8 [B, 960] (torch or NumPy) -> ctypes array of LmpcStackRobot (a copy on the host)."""
+    a = buf.cpu().numpy() if hasattr(buf, "cpu") else np.asarray(buf)
+    a = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1, ROBOT_BYTES)
+    return (N.LmpcStackRobot * a.shape[0]).from_buffer_copy(a.tobytes())
+
+
+def robots_view(buf) -> np.ndarray:
+    """uint8 [..., 960] -> NumPy structured array [...] with the fields of lmpc_stack_robot (STACK_ROBOT_DTYPE)."""
+    a = buf.cpu().numpy() if hasattr(buf, "cpu") else np.asarray(buf)
+    return np.ascontiguousarray(a, dtype=np.uint8).view(STACK_ROBOT_DTYPE)[..., 0]
+
+
+def _stream(stream, dev):
+    import torch
+
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    return s, ctypes.c_void_p(s.cuda_stream)
+
+
+def advance_device(solver: BatchedConvexQPSolver, cfg: N.LmpcRolloutCfg, d_robots, d_state, d_sim_out, stream=None):
+    """A batch of advances on the device (lmpc_stack_advance_device): d_robots uint8 [B][960] (in place), d_state uint8
+    [B][288], d_sim_out uint8 [B][472].  The commands are expanded into `solver`'s own record buffers, which
+    `solve_device` then solves."""
+    import torch
+
+    B = int(d_robots.shape[0]) if d_robots.dim() >= 1 else -1
+    dev = d_robots.device
+    check_device_tensor("d_robots", d_robots, torch.uint8, (B, ROBOT_BYTES), dev)
+    check_device_tensor("d_state", d_state, torch.uint8, (B, STATE_BYTES), dev)
+    check_device_tensor("d_sim_out", d_sim_out, torch.uint8, (B, S.OUT_BYTES), dev)
+    _, sp = _stream(stream, dev)
+    N.check(N.lib().lmpc_stack_advance_device(solver._ctx, ctypes.byref(cfg), d_robots.data_ptr(), d_state.data_ptr(),
+                                              d_sim_out.data_ptr(), B, sp), "lmpc_stack_advance_device")
+
+
+def solve_device(solver: BatchedConvexQPSolver, d_grf, d_status=None, d_iters=None, stream=None):
+    """Cold solves of the QPs the last `advance_device` left in `solver` (lmpc_stack_solve_device): d_grf float64
+    [B][H][12], d_status / d_iters int32 [B] or None."""
+    import torch
+
+    B = int(d_grf.shape[0]) if d_grf.dim() >= 1 else -1
+    dev = d_grf.device
+    check_device_tensor("d_grf", d_grf, torch.float64, (B, solver.H, 12), dev)
+    for name, t in (("d_status", d_status), ("d_iters", d_iters)):
+        if t is not None:
+            check_device_tensor(name, t, torch.int32, (B,), dev)
+    _, sp = _stream(stream, dev)
+    N.check(N.lib().lmpc_stack_solve_device(solver._ctx, B, d_grf.data_ptr(),
+                                            None if d_status is None else d_status.data_ptr(),
+                                            None if d_iters is None else d_iters.data_ptr(), sp),
+            "lmpc_stack_solve_device")
+
+
+def context_records(solver: BatchedConvexQPSolver, batch: int, stream=None):
+    """Copies (device tensors) of the first `batch` records [batch][33 + 12 H] and contact schedules [batch][H][4] in
+    `solver`'s own buffers, as the last expansion left them (lmpc_stack_copy_records_device)."""
+    import torch
+
+    dev = torch.device("cuda", torch.cuda.current_device())
+    d_rec = torch.empty((batch, solver.record_len), dtype=torch.float64, device=dev)
+    d_con = torch.empty((batch, solver.H, 4), dtype=torch.uint8, device=dev)
+    _, sp = _stream(stream, dev)
+    N.check(N.lib().lmpc_stack_copy_records_device(solver._ctx, int(batch), d_rec.data_ptr(), d_con.data_ptr(), sp),
+            "lmpc_stack_copy_records_device")
+    return d_rec, d_con
+
+
+def targets_device(d_robots, d_grf, template: N.LmpcWbcTarget, d_target, stream=None):
+    """A batch of WBC targets on the device (lmpc_stack_targets_device): d_robots uint8 [B][960]; d_grf float64
+    [B][H][12] or [B][12] (u_0 is read by stride); d_target uint8 [B][352]."""
+    import torch
+
+    B = int(d_robots.shape[0]) if d_robots.dim() >= 1 else -1
+    dev = d_robots.device
+    check_device_tensor("d_robots", d_robots, torch.uint8, (B, ROBOT_BYTES), dev)
+    check_device_tensor("d_target", d_target, torch.uint8, (B, TARGET_BYTES), dev)
+    if d_grf is None or not getattr(d_grf, "is_cuda", False) or d_grf.device != dev or d_grf.dtype != torch.float64 or \
+            d_grf.dim() not in (2, 3) or d_grf.shape[0] != B or d_grf.shape[-1] != 12 or not d_grf.is_contiguous():
+        raise ValueError("d_grf: expected a contiguous float64 device tensor [B][H][12] or [B][12]")
+    stride = d_grf.numel() // B
+    _, sp = _stream(stream, dev)
+    N.check(N.lib().lmpc_stack_targets_device(d_robots.data_ptr(), d_grf.data_ptr(), stride, ctypes.byref(template), B,
+                                              d_target.data_ptr(), sp), "lmpc_stack_targets_device")
+
+
+def candidates_device(d_sim_out, d_candidates, stream=None):
+    """held | touch of the plant's last step -> the next step's candidate contacts (lmpc_stack_candidates_device):
+    d_sim_out uint8 [B][472], d_candidates int32 [B][4]."""
+    import torch
+
+    B = int(d_sim_out.shape[0]) if d_sim_out.dim() >= 1 else -1
+    dev = d_sim_out.device
+    check_device_tensor("d_sim_out", d_sim_out, torch.uint8, (B, S.OUT_BYTES), dev)
+    check_device_tensor("d_candidates", d_candidates, torch.int32, (B, 4), dev)
+    _, sp = _stream(stream, dev)
+    N.check(N.lib().lmpc_stack_candidates_device(d_sim_out.data_ptr(), B, d_candidates.data_ptr(), sp),
+            "lmpc_stack_candidates_device")
+
+
+class StackLoop:
+    """The MPC, the whole-body controller and the plant closed into one device-resident loop.
+
+    Owns an MPC context (cold solves on the context's normal routing), a `WbcPipeline` and the target / candidate /
+    force buffers, all allocated once for `max_batch` robots."""
+
+    def __init__(self, model: N.LmpcRbdModel, params: N.LmpcParams, horizon: int, max_batch: int,
+                 rollout_cfg: N.LmpcRolloutCfg, sim_cfg: N.LmpcSimCfg, wbc_per_mpc: int, substeps: int = 1,
+                 template: N.LmpcWbcTarget = None, device: int = 0):
+        import torch
+
+        if max_batch < 1:
+            raise ValueError("max_batch must be positive")
+        if wbc_per_mpc < 1 or substeps < 1:
+            raise ValueError("wbc_per_mpc and substeps must be positive")
+        check_rates(params, sim_cfg, wbc_per_mpc, substeps)
+        if not sim_cfg.unilateral:
+            raise ValueError("the loop's candidate rule needs the plant's unilateral rule (sim_cfg.unilateral = 1)")
+        self.model, self.params, self.H = model, params, int(horizon)
+        self.max_batch, self.device = int(max_batch), device
+        self.rollout_cfg, self.sim_cfg = rollout_cfg, sim_cfg
+        self.wbc_per_mpc, self.substeps = int(wbc_per_mpc), int(substeps)
+        self.template = template if template is not None else wbc_target()
+        dev = torch.device("cuda", device)
+        self.solver = BatchedConvexQPSolver(params, self.H, max_batch=0, device=device)
+        N.check(N.lib().lmpc_stack_reserve(self.solver._ctx, self.max_batch), "lmpc_stack_reserve")
+        self.pipeline = WbcPipeline(model, self.max_batch, device)
+        self.d_grf = torch.zeros((self.max_batch, self.H, 12), dtype=torch.float64, device=dev)
+        self.d_qp_status = torch.zeros(self.max_batch, dtype=torch.int32, device=dev)
+        self.d_qp_iters = torch.zeros(self.max_batch, dtype=torch.int32, device=dev)
+        self.d_target = torch.zeros((self.max_batch, TARGET_BYTES), dtype=torch.uint8, device=dev)
+        self.d_candidates = torch.zeros((self.max_batch, 4), dtype=torch.int32, device=dev)
+
+    def close(self):
+        self.pipeline.close()
+        self.solver.close()
+
+    def run_device(self, d_robots, d_state, d_sim_out, mpc_ticks: int, log: bool = False, stream=None):
+        """`mpc_ticks` MPC ticks of params.dt each, every one followed by `wbc_per_mpc` low-level ticks; d_robots (uint8
+        [B][960]), d_state (uint8 [B][288]) and d_sim_out (uint8 [B][472]) are updated in place, so calls chain: n + m
+        ticks in one call leave the bits of n ticks followed by m.
+
+        log=True -> dict of device tensors.  Per MPC tick t: `robots` uint8 [T][B][960] (after the advance; its first
+        408 bytes are the command the QP was built from -- `cmd` is that view), `u0` float64 [T][B][12], `qp_status` /
+        `qp_iters` int32 [T][B], `target` uint8 [T][B][352].  Per low-level tick k = t * wbc_per_mpc + i: `states`
+        uint8 [K][B][288] and `out` uint8 [K][B][472] (after the plant step; `held`, `touch` int32 [K][B][4] and
+        `sim_status` int32 [K][B] are views of it), `tau` float64 [K][B][12], `candidates` int32 [K][B][4],
+        `wbc_status` int32 [K][B]."""
+        import torch
+
+        B = int(d_robots.shape[0]) if d_robots.dim() >= 1 else -1
+        if not 1 <= B <= self.max_batch:
+            raise ValueError(f"batch {B} outside 1..{self.max_batch}")
+        if mpc_ticks < 0:
+            raise ValueError("mpc_ticks must not be negative")
+        dev = torch.device("cuda", self.device)
+        check_device_tensor("d_robots", d_robots, torch.uint8, (B, ROBOT_BYTES), dev)
+        check_device_tensor("d_state", d_state, torch.uint8, (B, STATE_BYTES), dev)
+        check_device_tensor("d_sim_out", d_sim_out, torch.uint8, (B, S.OUT_BYTES), dev)
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        T, W = int(mpc_ticks), self.wbc_per_mpc
+        d_grf, d_qst, d_qit = self.d_grf[:B], self.d_qp_status[:B], self.d_qp_iters[:B]
+        d_target, d_cand = self.d_target[:B], self.d_candidates[:B]
+        logs = None
+        if log:
+            K = T * W
+            logs = dict(robots=torch.empty((T, B, ROBOT_BYTES), dtype=torch.uint8, device=dev),
+                        u0=torch.empty((T, B, 12), dtype=torch.float64, device=dev),
+                        qp_status=torch.empty((T, B), dtype=torch.int32, device=dev),
+                        qp_iters=torch.empty((T, B), dtype=torch.int32, device=dev),
+                        target=torch.empty((T, B, TARGET_BYTES), dtype=torch.uint8, device=dev),
+                        states=torch.empty((K, B, STATE_BYTES), dtype=torch.uint8, device=dev),
+                        out=torch.empty((K, B, S.OUT_BYTES), dtype=torch.uint8, device=dev),
+                        tau=torch.empty((K, B, 12), dtype=torch.float64, device=dev),
+                        candidates=torch.empty((K, B, 4), dtype=torch.int32, device=dev),
+                        wbc_status=torch.empty((K, B), dtype=torch.int32, device=dev))
+        with torch.cuda.stream(s):
+            for t in range(T):
+                advance_device(self.solver, self.rollout_cfg, d_robots, d_state, d_sim_out, s)
+                solve_device(self.solver, d_grf, d_qst, d_qit, s)
+                targets_device(d_robots, d_grf, self.template, d_target, s)
+                if log:
+                    logs["robots"][t].copy_(d_robots)
+                    logs["u0"][t].copy_(d_grf[:, 0])
+                    logs["qp_status"][t].copy_(d_qst)
+                    logs["qp_iters"][t].copy_(d_qit)
+                    logs["target"][t].copy_(d_target)
+                for i in range(W):
+                    candidates_device(d_sim_out, d_cand, s)
+                    d_x, d_wst = self.pipeline.solve_device(d_state, d_target, s)
+                    d_tau = d_x[:, S.TAU_OFFSET:S.TAU_OFFSET + 12]
+                    S.step_device(self.model, self.sim_cfg, d_state, d_tau, d_cand, d_state, d_sim_out, self.substeps, s)
+                    if log:
+                        k = t * W + i
+                        logs["states"][k].copy_(d_state)
+                        logs["out"][k].copy_(d_sim_out)
+                        logs["tau"][k].copy_(d_tau)
+                        logs["candidates"][k].copy_(d_cand)
+                        logs["wbc_status"][k].copy_(d_wst)
+        if log:
+            flags = logs["out"].view(torch.int32)[..., S.OUT_BYTES // 4 - 10:]  # held (4), touch (4), status, reserved
+            logs["cmd"] = logs["robots"][..., :N.COMMAND_BYTES]
+            logs["held"], logs["touch"], logs["sim_status"] = flags[..., 0:4], flags[..., 4:8], flags[..., 8]
+        return logs

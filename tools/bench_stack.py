@@ -1,0 +1,146 @@
+#!/usr/bin/env python3
+"""Benchmark of the full loop (include/lmpc/lmpc_stack.h: MPC -> WBC -> rigid-body plant) on MI355X.
+
+    python tools/bench_stack.py [--ticks T] [--repeats R] [--out FILE]
+
+1024 and 4096 Go1 trot robots from a standing pose with seeded commands, H = 10, the reference's rates (10 ms MPC tick,
+8 low-level ticks of 1.25 ms).  One HIP event pair around a whole `StackLoop.run_device` of T MPC ticks, after a
+warm-up run from the same start; the best of R repeats.  In the same process, from the same start:
+
+    solve_only   the T ticks' commands (logged by the warm-up run) through lmpc_solve_commands_device alone, one call
+                 per tick -- tools/bench_rollout.py's solve-only tick
+    wbc_sim      the 8 T low-level ticks replayed: what one sim.WbcSim tick does (WbcPipeline.solve_device, then
+                 lmpc_sim_step_device) on the logged state, targets and candidates of each tick.  The hierarchical
+                 solve's time depends on its data, so the parts run on the loop's own data, not on constant targets.
+
+glue_us_per_mpc_tick = the whole - solve_only - the 8 replayed wbc_sim ticks: the advance launch (which also expands
+the records), the targets launch and the 8 candidate launches, with their host calls.  Prints ONE JSON line.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+BATCHES = (1024, 4096)
+H, WBC_PER_MPC, SIM_DT = 10, 8, 0.00125
+
+
+def timed(fn, repeats):
+    import torch
+
+    best = float("inf")
+    for _ in range(repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        best = min(best, a.elapsed_time(b))
+    return best
+
+
+def start_of(batch, seed):
+    """Standing Go1 robots (joints 0, 0.8, -1.6; the feet on the ground) at seeded places and headings, with seeded
+    commands -> (robots, states, first outs) as uint8 arrays."""
+    from legged_mpc_control_amd import _native as N, rbd, rollout, stack
+
+    rng = np.random.default_rng(seed)
+    cfg, model = rollout.cfg_go1(), rbd.model_go1()
+    s = np.zeros(36)
+    s[6:18] = np.tile([0.0, 0.8, -1.6], 4)
+    z = -rbd.terms_dict(rbd.compute(model, rbd.state_from_vector(s)))["foot_pos"][2]
+    robots, states, outs = [], [], []
+    for _ in range(batch):
+        s[0] = rng.uniform(-3.0, 3.0)
+        s[3:6] = [rng.uniform(-1.0, 1.0), rng.uniform(-1.0, 1.0), z]
+        st = rbd.state_from_vector(s)
+        rb, o = stack.robot_init(cfg, model, st, (rng.uniform(-0.4, 0.4), rng.uniform(-0.2, 0.2)),
+                                 rng.uniform(-0.3, 0.3), z, N.GAIT_TROT, 4.0)
+        robots.append(rb)
+        states.append(st)
+        outs.append(o)
+    return tuple(stack.to_bytes(x) for x in (robots, states, outs))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ticks", type=int, default=50)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+
+    from legged_mpc_control_amd import BatchedConvexQPSolver, rbd, rollout, sim, stack, synth
+
+    dev = torch.device("cuda:0")
+    T = args.ticks
+    rows = []
+    for batch in BATCHES:
+        p, cfg, model = synth.params(), rollout.cfg_go1(), rbd.model_go1()
+        loop = stack.StackLoop(model, p, H, batch, cfg, sim.cfg(dt=SIM_DT, ground_z=0.0), WBC_PER_MPC)
+        start = [torch.from_numpy(a).to(dev) for a in start_of(batch, 4000 + batch)]
+        bufs = [a.clone() for a in start]
+        log = loop.run_device(*bufs, T, log=True)  # warm-up, and the record of what the run does
+        torch.cuda.synchronize()
+        x = log["states"].view(torch.float64)
+        row = dict(batch=batch, H=H, mpc_ticks=T, wbc_per_mpc=WBC_PER_MPC, dense_path=loop.solver.dense_path,
+                   nonzero_status=dict(qp=int((log["qp_status"] != 0).sum()), wbc=int((log["wbc_status"] != 0).sum()),
+                                       sim=int((log["sim_status"] != 0).sum())),
+                   fallen=int(((x[:, :, 1].abs() > 0.5) | (x[:, :, 2].abs() > 0.5) |
+                               (x[:, :, 5] < 0.5 * x[0, :, 5])).any(dim=0).sum()))
+        cmds = log["cmd"].contiguous()
+
+        def whole():
+            for d, s in zip(bufs, start):
+                d.copy_(s)
+            loop.run_device(*bufs, T)
+
+        ms = timed(whole, args.repeats)
+        row["whole"] = dict(ms_per_mpc_tick=ms / T, robot_ticks_per_s=batch * T / (ms * 1e-3))
+        grf = torch.empty((batch, H, 12), dtype=torch.float64, device=dev)
+        solver = BatchedConvexQPSolver(p, H, max_batch=0)
+
+        def solve_only():
+            for t in range(T):
+                solver.solve_commands_device(cmds[t], grf)
+
+        solve_only()
+        torch.cuda.synchronize()
+        ms_solve = timed(solve_only, args.repeats)
+        row["solve_only"] = dict(ms_per_tick=ms_solve / T)
+        pipe = loop.pipeline  # the loop's own pipeline: the same buffers, nothing new allocated
+        d_sim_cfg = loop.sim_cfg
+        prev = [start[1]] + [log["states"][k] for k in range(WBC_PER_MPC * T - 1)]
+        d_next, d_o = torch.empty_like(start[1]), torch.empty_like(start[2])
+
+        def wbc_sim():
+            for k in range(WBC_PER_MPC * T):
+                d_x, _ = pipe.solve_device(prev[k], log["target"][k // WBC_PER_MPC])
+                sim.step_device(model, d_sim_cfg, prev[k], d_x[:, sim.TAU_OFFSET:sim.TAU_OFFSET + 12],
+                                log["candidates"][k], d_next, d_o, 1)
+
+        wbc_sim()
+        torch.cuda.synchronize()
+        ms_ws = timed(wbc_sim, args.repeats)
+        row["wbc_sim"] = dict(ms_per_tick=ms_ws / (WBC_PER_MPC * T))
+        row["glue_us_per_mpc_tick"] = 1e3 * (ms - ms_solve - ms_ws) / T
+        rows.append(row)
+        solver.close()
+        loop.close()
+    line = json.dumps(dict(bench="stack", device=torch.cuda.get_device_name(0), configs=rows))
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

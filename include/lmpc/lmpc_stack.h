@@ -18,7 +18,9 @@
  * One MPC tick of a robot (`lmpc_stack_robot`), period params.dt:
  *
  *   advance (before the solve), from the robot's lmpc_rbd_state and the plant's latest lmpc_sim_out:
- *     1. feedback -- stands in for the estimator (BaseInterface.cpp:511-518 read backwards):
+ *     1. feedback (BaseInterface.cpp:511-518 read backwards) -- from the plant's own state and block, or, when the
+ *        caller runs the estimator of lmpc_est.h between the plant and this call, from its state_est and its shadow
+ *        lmpc_sim_out (stack.StackLoop's `estimator` option does):
  *          cmd.state.root_euler = (roll, pitch, yaw) = (state.euler[2], state.euler[1], state.euler[0])
  *          root_pos, root_ang_vel (world), root_lin_vel (world) copied
  *          foot_pos_world[l] = sim_out.foot_pos[l]            the measured feet (state.fbk.foot_pos_world), all four
@@ -61,7 +63,8 @@
  * Chosen here, not restated:
  *   - Zero latency: an MPC tick's result is applied to the low-level ticks that follow it at once.  The reference's
  *     MPC and low-level loops are asynchronous threads; the delay between them is not modelled.
- *   - The feedback is the plant's own state: no estimator, no sensor noise.
+ *   - The feedback is whatever lmpc_rbd_state / lmpc_sim_out the caller passes: the plant's own (perfect state
+ *     knowledge), or the estimate of lmpc_est.h (the reference's BasicKF on a sensor model of the plant, with noise).
  *   - touch as the contact flag, the candidate rule above, and mode 0's FSM targets (see 3.).
  *   - Nothing special is done for a robot whose QP, WBC chain or plant step reports a non-zero status: it continues
  *     on what those stages return -- the QP's forces as they are (zeros for LMPC_QP_NAN), the hierarchical solver's

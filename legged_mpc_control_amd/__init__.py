@@ -6,12 +6,13 @@ the solve run as one fused HIP kernel for gfx950 behind the C-ABI in
 include/lmpc/lmpc.h.
 """
 from . import _native
-from ._native import (GAIT_CRAWL, GAIT_STAND, GAIT_TROT, GAIT_TROT_WITH_STAND, LmpcCommand, LmpcLegKin,
-                      LmpcOptions, LmpcParams, LmpcRbdModel, LmpcRbdState, LmpcRbdTerms, LmpcRobot, LmpcRolloutCfg,
-                      LmpcRolloutLog, LmpcSimCfg, LmpcSimOut, LmpcStackRobot, LmpcWbcTarget, NativeLibraryError)
+from ._native import (GAIT_CRAWL, GAIT_STAND, GAIT_TROT, GAIT_TROT_WITH_STAND, LmpcCommand, LmpcEstCfg, LmpcEstFilter,
+                      LmpcEstOut, LmpcEstSensors, LmpcLegKin, LmpcOptions, LmpcParams, LmpcRbdModel, LmpcRbdState,
+                      LmpcRbdTerms, LmpcRobot, LmpcRolloutCfg, LmpcRolloutLog, LmpcSimCfg, LmpcSimOut, LmpcStackRobot,
+                      LmpcWbcTarget, NativeLibraryError)
 from .solver import (BatchedConvexQPSolver, ConvexQPSolver, LeggedContactFSM, LeggedCtrl, LeggedFeedback,
                      LeggedParam, LeggedState, foot_jacobian, grf_to_torque, leg_kin_default, solver_options)
-from . import rbd, rollout, sim, stack, synth
+from . import est, rbd, rollout, sim, stack, synth
 from .rbd import WbcPipeline
 from .sim import WbcSim
 from .stack import StackLoop
@@ -25,4 +26,5 @@ __all__ = [
     "rbd", "WbcPipeline", "LmpcRbdModel", "LmpcRbdState", "LmpcRbdTerms", "LmpcWbcTarget",
     "sim", "WbcSim", "LmpcSimCfg", "LmpcSimOut",
     "stack", "StackLoop", "LmpcStackRobot",
+    "est", "LmpcEstCfg", "LmpcEstSensors", "LmpcEstFilter", "LmpcEstOut",
 ]

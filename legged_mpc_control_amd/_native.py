@@ -82,6 +82,13 @@ STACK_SYMBOLS = (
     "lmpc_stack_copy_records_device", "lmpc_stack_targets_device", "lmpc_stack_candidates_device",
 )
 STACK_ABI_VERSION = 1
+# include/lmpc/lmpc_est.h: the sensor model and the base-state Kalman filter
+EST_SYMBOLS = (
+    "lmpc_est_abi_version", "lmpc_est_sensors_size", "lmpc_est_cfg_size", "lmpc_est_filter_size", "lmpc_est_out_size",
+    "lmpc_est_cfg_default", "lmpc_est_sensors_from_plant", "lmpc_est_init", "lmpc_est_report", "lmpc_est_update",
+    "lmpc_est_feedback", "lmpc_est_sensors_from_plant_device", "lmpc_est_init_device", "lmpc_est_update_device",
+)
+EST_ABI_VERSION = 1
 
 
 class LmpcParams(ctypes.Structure):
@@ -267,6 +274,38 @@ class LmpcStackRobot(ctypes.Structure):
 
 
 STACK_ROBOT_BYTES = ctypes.sizeof(LmpcStackRobot)  # 960
+
+
+class LmpcEstSensors(ctypes.Structure):
+    _fields_ = [
+        ("imu_acc", ctypes.c_double * 3), ("imu_ang_vel", ctypes.c_double * 3), ("euler", ctypes.c_double * 3),
+        ("joint_pos", ctypes.c_double * 12), ("joint_vel", ctypes.c_double * 12), ("contact", ctypes.c_double * 4),
+    ]
+
+
+class LmpcEstCfg(ctypes.Structure):
+    _fields_ = [
+        ("dt", ctypes.c_double), ("noise_pimu", ctypes.c_double), ("noise_vimu", ctypes.c_double),
+        ("noise_pfoot", ctypes.c_double), ("noise_pimu_rel_foot", ctypes.c_double),
+        ("noise_vimu_rel_foot", ctypes.c_double), ("noise_zfoot", ctypes.c_double), ("gravity", ctypes.c_double),
+        ("drift_threshold", ctypes.c_double), ("drift_divisor", ctypes.c_double), ("init_P", ctypes.c_double),
+        ("sigma_acc", ctypes.c_double), ("sigma_gyro", ctypes.c_double), ("sigma_euler", ctypes.c_double),
+        ("sigma_joint_pos", ctypes.c_double), ("sigma_joint_vel", ctypes.c_double), ("seed", ctypes.c_uint64),
+        ("assume_flat_ground", ctypes.c_int32), ("reserved", ctypes.c_int32),
+    ]
+
+
+class LmpcEstFilter(ctypes.Structure):
+    _fields_ = [("x", ctypes.c_double * 18), ("P", ctypes.c_double * 324), ("inited", ctypes.c_int32),
+                ("ticks", ctypes.c_int32)]
+
+
+class LmpcEstOut(ctypes.Structure):
+    _fields_ = [
+        ("foot_pos_rel", ctypes.c_double * 12), ("foot_pos_world", ctypes.c_double * 12),
+        ("foot_vel_world", ctypes.c_double * 12), ("estimated_contacts", ctypes.c_int32 * 4),
+        ("status", ctypes.c_int32), ("reserved", ctypes.c_int32),
+    ]
 
 
 class NativeLibraryError(RuntimeError):
@@ -500,6 +539,35 @@ def lib():
             raise NativeLibraryError(f"{path}: lmpc_stack.h ABI {L.lmpc_stack_abi_version()} / lmpc_stack_robot of "
                                      f"{L.lmpc_stack_robot_size()} B, this binding is ABI {STACK_ABI_VERSION} / "
                                      f"{STACK_ROBOT_BYTES} B")
+        esp, ecp = ctypes.POINTER(LmpcEstSensors), ctypes.POINTER(LmpcEstCfg)
+        efp, eop = ctypes.POINTER(LmpcEstFilter), ctypes.POINTER(LmpcEstOut)
+        for name in ("lmpc_est_abi_version", "lmpc_est_sensors_size", "lmpc_est_cfg_size", "lmpc_est_filter_size",
+                     "lmpc_est_out_size"):
+            getattr(L, name).restype = ctypes.c_int
+        L.lmpc_est_cfg_default.argtypes = [ecp]
+        L.lmpc_est_cfg_default.restype = None
+        L.lmpc_est_sensors_from_plant.argtypes = [mp, ecp, sp, sop, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int, esp]
+        L.lmpc_est_sensors_from_plant.restype = ctypes.c_int
+        L.lmpc_est_init.argtypes = [mp, ecp, esp, dp, efp]
+        L.lmpc_est_init.restype = ctypes.c_int
+        L.lmpc_est_report.argtypes = [mp, esp, efp, sp, eop]
+        L.lmpc_est_report.restype = ctypes.c_int
+        L.lmpc_est_update.argtypes = [mp, ecp, esp, efp, sp, eop]
+        L.lmpc_est_update.restype = ctypes.c_int
+        L.lmpc_est_feedback.argtypes = [sop, eop, sop]
+        L.lmpc_est_feedback.restype = ctypes.c_int
+        L.lmpc_est_sensors_from_plant_device.argtypes = [mp, ecp, vp, vp, ctypes.c_int, ctypes.c_int32, ctypes.c_uint32,
+                                                         vp, ctypes.c_int64, vp, vp]
+        L.lmpc_est_sensors_from_plant_device.restype = ctypes.c_int
+        L.lmpc_est_init_device.argtypes = [mp, ecp, vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp, vp, vp, vp, vp]
+        L.lmpc_est_init_device.restype = ctypes.c_int
+        L.lmpc_est_update_device.argtypes = [mp, ecp, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp]
+        L.lmpc_est_update_device.restype = ctypes.c_int
+        est_sizes = (L.lmpc_est_sensors_size(), L.lmpc_est_cfg_size(), L.lmpc_est_filter_size(), L.lmpc_est_out_size())
+        est_mirrors = tuple(ctypes.sizeof(c) for c in (LmpcEstSensors, LmpcEstCfg, LmpcEstFilter, LmpcEstOut))
+        if L.lmpc_est_abi_version() != EST_ABI_VERSION or est_sizes != est_mirrors:
+            raise NativeLibraryError(f"{path}: lmpc_est.h ABI {L.lmpc_est_abi_version()} with struct sizes {est_sizes}, "
+                                     f"this binding is ABI {EST_ABI_VERSION} with {est_mirrors}")
         if L.lmpc_rollout_abi_version() != ROLLOUT_ABI_VERSION or L.lmpc_robot_size() != ROBOT_BYTES:
             raise NativeLibraryError(f"{path}: lmpc_rollout.h ABI {L.lmpc_rollout_abi_version()} / lmpc_robot of "
                                      f"{L.lmpc_robot_size()} B, this binding is ABI {ROLLOUT_ABI_VERSION} / {ROBOT_BYTES} B")

@@ -1,0 +1,345 @@
+// lmpc_est.hip -- the batched state estimator of include/lmpc/lmpc_est.h: the sensor model and BasicKF's update, on
+// the host (one robot) and on the device (a batch).
+//
+// The arithmetic is lmpc_est_common.h's, compiled for both sides.  Device mapping of the update: a group of 32 lanes
+// per robot, two robots per wavefront, one wavefront per block.  Lane j < 18 of a group owns column j of P (18 doubles
+// in registers; P is symmetric to the bit, so the column is read and written as row j of the stored matrix, 144
+// contiguous bytes) and element j of x.
+//   1. lanes 0-3 run leg_pass for their leg (base at the origin and at rest) and leave fk and J_leg qd in LDS;
+//   2. lane i < 28 forms y_i and R_ii and leaves them in LDS; lane j forms column j of Pbar = A P A' + Q (the lanes
+//      0-2 also read column j + 3 of P) and its element of xbar;
+//   3. the 28 scalar measurement updates, fully unrolled: lane j takes v_j = (c P)_j from its own column (row i of C
+//      has at most two entries, +-1), the group exchanges v and x through LDS (one 16-byte write per lane, broadcast
+//      reads, double buffered: one barrier per update), then every lane forms s and the innovation and updates its
+//      element of x and its column;
+//   4. the drift rule on the 2 x 2 block (lanes 0 and 1 publish it), the finiteness vote of the group, the stores:
+//      lane j its column and element of x, lane 0 the tick count, the lanes 0-3 their leg's part of state_est / lmpc_est_out /
+//      the shadow lmpc_sim_out, lane 4 the base's part, and all 32 lanes the copied words of the shadow.
+// No 28 x 28 matrix, no scratch, no workspace; 1744 B of LDS per robot.  The lanes 18-31 of a group repeat column 17 and
+// store nothing; a group past the batch repeats the last robot and stores nothing.
+//
+// leg_pass indexes the model by the leg's number: as in lmpc_sim.hip, a lane copies its leg's kinematic constants into
+// slot 0 of a private model and calls leg_pass(..., leg 0), so that every index is a compile-time constant.
+#include <hip/hip_runtime.h>
+
+#include "lmpc/lmpc_est.h"
+#include "lmpc_est_common.h"
+
+static_assert(sizeof(lmpc_est_sensors) == 296, "lmpc_est_sensors layout (legged_mpc_control_amd/_native.py)");
+static_assert(sizeof(lmpc_est_cfg) == 144, "lmpc_est_cfg layout");
+static_assert(sizeof(lmpc_est_filter) == 2744, "lmpc_est_filter layout");
+static_assert(sizeof(lmpc_est_out) == 312, "lmpc_est_out layout");
+static_assert(sizeof(lmpc_sim_out) == 472 && offsetof(lmpc_sim_out, foot_pos) == 240 &&
+                  offsetof(lmpc_sim_out, held) == 432 && offsetof(lmpc_sim_out, touch) == 448,
+              "lmpc_sim_out layout (the shadow copy below)");
+
+namespace lmpc_est {
+namespace {
+
+constexpr int BLOCK = 64;                    // one wavefront per block
+constexpr int GROUP = 32;                    // lanes per robot
+constexpr int BLOCK_ROBOTS = BLOCK / GROUP;  // 2
+constexpr int ONE_THREADS = 64;              // the one-thread-per-robot kernels (sensors, init)
+
+#if defined(__HIPCC__)
+struct Shared {
+    double kin[4][6];  // per leg: fk, J_leg qd
+    double y[NY], r[NY];
+    double vx[2][GROUP][2];  // v_j, x_j; a slot for every lane, so that the store needs no branch
+    double xf[6];         // the new pos, vel
+    double blk[4];     // P00, P10, P01, P11
+};
+
+__global__ void __launch_bounds__(BLOCK)
+    lmpc_est_update_kernel(const lmpc_rbd_model md, const lmpc_est_cfg cfg, const lmpc_est_sensors* __restrict__ sns,
+                           int batch, lmpc_est_filter* filters, lmpc_rbd_state* ses, lmpc_est_out* outs,
+                           const lmpc_sim_out* __restrict__ sos, lmpc_sim_out* shs) {
+    __shared__ Shared shared[BLOCK_ROBOTS];
+    const int g = threadIdx.x / GROUP, j = threadIdx.x % GROUP;
+    const int robot = blockIdx.x * BLOCK_ROBOTS + g;
+    // a group past the batch computes the last robot again and stores nothing: the barriers below stay uniform
+    const bool active = robot < batch;
+    const int rb = active ? robot : batch - 1;
+    Shared& sh = shared[g];
+    const lmpc_est_sensors& sn = sns[rb];
+    lmpc_est_filter& f = filters[rb];
+
+    // 1
+    if (j < 4) {
+        lmpc_rbd_model lm{};
+        lmpc_rbd_state js{};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) lm.joint_origin[k][i] = md.joint_origin[3 * j + k][i];
+            js.joint_pos[k] = sn.joint_pos[3 * j + k], js.joint_vel[k] = sn.joint_vel[3 * j + k];
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) lm.foot[0][i] = md.foot[j][i];
+        const LegKin k = leg_kin(lm, js, 0);
+        sh.kin[j][0] = k.fk.x, sh.kin[j][1] = k.fk.y, sh.kin[j][2] = k.fk.z;
+        sh.kin[j][3] = k.fv.x, sh.kin[j][4] = k.fv.y, sh.kin[j][5] = k.fv.z;
+    }
+    const M3 R = rot_of(sn.euler);
+    const V3 wb = v3(sn.imu_ang_vel[0], sn.imu_ang_vel[1], sn.imu_ang_vel[2]);
+    double xj, Pc[NX];
+    const int jc = j < NX ? j : NX - 1;
+    {
+        double Pj[NX], Pj3[NX];
+        const double x0j = f.x[jc], x0j3 = f.x[jc < 3 ? jc + 3 : jc];
+        const double x0z = f.x[2];
+        const V3 x0v = v3(f.x[3], f.x[4], f.x[5]);
+        const double* pj = f.P + jc * NX;
+        const double* pj3 = f.P + (jc < 3 ? jc + 3 : jc) * NX;
+#pragma unroll
+        for (int r = 0; r < NX; ++r) Pj[r] = pj[r], Pj3[r] = pj3[r];
+        __syncthreads();
+        // 2
+        if (j < NY) {
+            const int l = meas_leg(j);
+            const LegKin k{v3(sh.kin[l][0], sh.kin[l][1], sh.kin[l][2]), v3(sh.kin[l][3], sh.kin[l][4], sh.kin[l][5])};
+            double y, r;
+            meas_value(cfg, j, R, wb, k, sn.contact[l], x0z, x0v, y, r);
+            sh.y[j] = y, sh.r[j] = r;
+        }
+        pbar_col(jc, Pj, Pj3, cfg.dt, q_diag(cfg, jc, sn.contact), Pc);
+        const V3 u = input_u(cfg, R, sn.imu_acc);
+        xj = xbar_elem(jc, x0j, x0j3, cfg.dt, u.x, u.y, u.z);
+    }
+    bool bad = f.inited == 0;
+    __syncthreads();
+
+    // 3
+#pragma unroll
+    for (int i = 0; i < NY; ++i) {
+        const int p = meas_p(i), q = meas_q(i);
+        const double vj = row_v(Pc, p, q);
+        double(*vb)[2] = sh.vx[i & 1];
+        // unconditional: a branch here splits the unrolled loop into blocks, and the compiler then sinks the updates of
+        // rows that are read much later out of the loop, keeping every update's v alive for them (900 spills)
+        vb[j][0] = vj, vb[j][1] = xj;
+        __syncthreads();
+        const int pp = p < 0 ? 0 : p;
+        double v[NX], inv_s, gain_e;
+#pragma unroll
+        for (int r = 0; r < NX; ++r) v[r] = vb[r][0];
+        bad = !step_gain(v[pp], v[q], p < 0, sh.r[i], sh.y[i], vb[pp][1], vb[q][1], inv_s, gain_e) || bad;
+        xj = step_x(xj, vj, gain_e);
+        step_col(Pc, v, vj, inv_s);
+        // A row of the column that no later update reads (the rows 6, 7 after the first update, ...) is needed only
+        // by the stores after the loop, and the compiler sinks its remaining updates there, with v, v_j and 1 / s of
+        // every update alive until then: 900 spilled registers.  The empty asm pins each update where it stands.
+#pragma unroll
+        for (int r = 0; r < NX; ++r) asm volatile("" : "+v"(Pc[r]));
+    }
+
+    // 4
+    if (j == 0) sh.blk[0] = Pc[0], sh.blk[1] = Pc[1];
+    if (j == 1) sh.blk[2] = Pc[0], sh.blk[3] = Pc[1];
+    __syncthreads();
+    if (drift_det(sh.blk[0], sh.blk[3], sh.blk[2], sh.blk[1]) > cfg.drift_threshold) drift_col(jc, Pc, cfg.drift_divisor);
+    bool col_bad = false;
+#pragma unroll
+    for (int r = 0; r < NX; ++r) col_bad = col_bad || !finite(Pc[r]);
+    col_bad = col_bad || !finite(xj);
+    if (j < 6) sh.xf[j] = xj;
+    const unsigned long long votes = __ballot(col_bad ? 1 : 0);
+    const bool failed = bad || ((votes >> (g * GROUP)) & 0xffffffffull) != 0;
+    __syncthreads();
+    const double x[6] = {sh.xf[0], sh.xf[1], sh.xf[2], sh.xf[3], sh.xf[4], sh.xf[5]};
+
+    if (active && !failed) {
+        if (j < NX) {
+            double* pj = f.P + j * NX;
+#pragma unroll
+            for (int r = 0; r < NX; ++r) pj[r] = Pc[r];
+            f.x[j] = xj;
+        }
+        if (j == 0) f.ticks = f.ticks + 1;
+    }
+    if (!active) return;
+    const lmpc_sim_out* so = sos ? sos + rb : nullptr;
+    lmpc_sim_out* shd = shs ? shs + rb : nullptr;
+    if (shd) {
+        // the words of the plant's block that the shadow keeps: qdd and force (0-29), held (54, 55), status (58)
+        const unsigned long long* src = reinterpret_cast<const unsigned long long*>(so);
+        unsigned long long* dst = reinterpret_cast<unsigned long long*>(shd);
+        if (j < 30) dst[j] = src[j];
+        if (j == 30) dst[54] = src[54];
+        if (j == 31) dst[55] = src[55], dst[58] = src[58];
+    }
+    if (j < 4) {
+        const LegKin k{v3(sh.kin[j][0], sh.kin[j][1], sh.kin[j][2]), v3(sh.kin[j][3], sh.kin[j][4], sh.kin[j][5])};
+        LegReport o = report_leg(R, wb, k, x);
+        const V3 zero = v3(0.0, 0.0, 0.0);
+        if (failed) o.rel = zero, o.world = zero, o.vel = zero;
+        const int ec = failed ? 0 : (sn.contact[j] < 0.5 ? 0 : 1);
+        if (ses) {
+            lmpc_rbd_state& se = ses[rb];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                se.joint_pos[3 * j + i] = failed ? 0.0 : sn.joint_pos[3 * j + i];
+                se.joint_vel[3 * j + i] = failed ? 0.0 : sn.joint_vel[3 * j + i];
+            }
+        }
+        if (outs) {
+            lmpc_est_out& eo = outs[rb];
+            eo.foot_pos_rel[3 * j] = o.rel.x, eo.foot_pos_rel[3 * j + 1] = o.rel.y, eo.foot_pos_rel[3 * j + 2] = o.rel.z;
+            eo.foot_pos_world[3 * j] = o.world.x, eo.foot_pos_world[3 * j + 1] = o.world.y;
+            eo.foot_pos_world[3 * j + 2] = o.world.z;
+            eo.foot_vel_world[3 * j] = o.vel.x, eo.foot_vel_world[3 * j + 1] = o.vel.y, eo.foot_vel_world[3 * j + 2] = o.vel.z;
+            eo.estimated_contacts[j] = ec;
+        }
+        if (shd) {
+            shd->foot_pos[3 * j] = o.world.x, shd->foot_pos[3 * j + 1] = o.world.y, shd->foot_pos[3 * j + 2] = o.world.z;
+            shd->foot_vel[3 * j] = o.vel.x, shd->foot_vel[3 * j + 1] = o.vel.y, shd->foot_vel[3 * j + 2] = o.vel.z;
+            shd->touch[j] = ec;
+        }
+    }
+    if (j == 4) {
+        if (ses) {
+            lmpc_rbd_state& se = ses[rb];
+            const V3 w = world_omega(R, sn.imu_ang_vel);
+            const double wv[3] = {w.x, w.y, w.z};
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                se.euler[i] = failed ? 0.0 : sn.euler[i], se.pos[i] = failed ? 0.0 : x[i];
+                se.omega[i] = failed ? 0.0 : wv[i], se.lin_vel[i] = failed ? 0.0 : x[3 + i];
+            }
+        }
+        if (outs) outs[rb].status = failed ? 1 : 0, outs[rb].reserved = 0;
+    }
+}
+
+__global__ void __launch_bounds__(ONE_THREADS)
+    lmpc_est_sensors_kernel(const lmpc_rbd_model md, const lmpc_est_cfg cfg, const lmpc_rbd_state* __restrict__ states,
+                            const lmpc_sim_out* __restrict__ sos, int batch, int32_t index0, uint32_t tick,
+                            const int32_t* __restrict__ gaits, long long gait_stride, lmpc_est_sensors* sns) {
+    const int b = blockIdx.x * ONE_THREADS + threadIdx.x;
+    if (b >= batch) return;
+    const bool stand = gaits && gaits[(long long)b * gait_stride] == LMPC_GAIT_STAND;
+    sensors_from_plant(md, cfg, states[b], sos[b], index0 + b, tick, stand, sns[b]);  // in place: no private copy
+}
+
+__global__ void __launch_bounds__(ONE_THREADS)
+    lmpc_est_init_kernel(const lmpc_rbd_model md, const lmpc_est_cfg cfg, const lmpc_est_sensors* __restrict__ sns,
+                         const double* __restrict__ pos0, long long pos0_stride, int batch, lmpc_est_filter* filters,
+                         lmpc_rbd_state* ses, lmpc_est_out* outs, const lmpc_sim_out* sos, lmpc_sim_out* shs) {
+    const int b = blockIdx.x * ONE_THREADS + threadIdx.x;
+    if (b >= batch) return;
+    double p0[3] = {0.0, 0.0, 0.09};
+    if (pos0)
+        for (int i = 0; i < 3; ++i) p0[i] = pos0[(long long)b * pos0_stride + i];
+    init_robot(md, cfg, sns[b], p0, filters[b]);
+    lmpc_est_out eo;
+    report_robot(md, sns[b], filters[b], ses ? ses + b : nullptr, &eo);
+    if (outs) outs[b] = eo;
+    if (shs) feedback_robot(sos[b], eo, shs[b]);
+}
+#endif
+
+int launch_rc() {
+    const hipError_t e = hipGetLastError();
+    if (e == hipErrorInvalidDeviceFunction || e == hipErrorNoBinaryForGpu) return LMPC_ERR_NOT_BUILT;
+    return e == hipSuccess ? LMPC_OK : LMPC_ERR_LAUNCH;
+}
+
+}  // namespace
+}  // namespace lmpc_est
+
+using namespace lmpc_est;
+
+extern "C" int lmpc_est_abi_version(void) { return LMPC_EST_ABI_VERSION; }
+extern "C" int lmpc_est_sensors_size(void) { return (int)sizeof(lmpc_est_sensors); }
+extern "C" int lmpc_est_cfg_size(void) { return (int)sizeof(lmpc_est_cfg); }
+extern "C" int lmpc_est_filter_size(void) { return (int)sizeof(lmpc_est_filter); }
+extern "C" int lmpc_est_out_size(void) { return (int)sizeof(lmpc_est_out); }
+
+extern "C" void lmpc_est_cfg_default(lmpc_est_cfg* cfg) {
+    if (!cfg) return;
+    *cfg = lmpc_est_cfg{};
+    cfg->dt = 0.00125;
+    cfg->noise_pimu = 0.01, cfg->noise_vimu = 0.01, cfg->noise_pfoot = 0.01;
+    cfg->noise_pimu_rel_foot = 0.001, cfg->noise_vimu_rel_foot = 0.1, cfg->noise_zfoot = 0.001;
+    cfg->gravity = 9.81;
+    cfg->drift_threshold = 1e-6, cfg->drift_divisor = 10.0;
+    cfg->init_P = 3.0;
+    cfg->assume_flat_ground = 1;
+}
+
+extern "C" int lmpc_est_sensors_from_plant(const lmpc_rbd_model* model, const lmpc_est_cfg* cfg,
+                                           const lmpc_rbd_state* state, const lmpc_sim_out* sim_out, int32_t robot_index,
+                                           uint32_t tick, int stand, lmpc_est_sensors* sensors) {
+    if (!model || !cfg || !state || !sim_out || !sensors || !good_sigmas(*cfg)) return LMPC_ERR_ARG;
+    sensors_from_plant(*model, *cfg, *state, *sim_out, robot_index, tick, stand != 0, *sensors);
+    return LMPC_OK;
+}
+
+extern "C" int lmpc_est_init(const lmpc_rbd_model* model, const lmpc_est_cfg* cfg, const lmpc_est_sensors* sensors,
+                             const double* pos0, lmpc_est_filter* filter) {
+    if (!model || !cfg || !sensors || !filter) return LMPC_ERR_ARG;
+    init_robot(*model, *cfg, *sensors, pos0, *filter);
+    return LMPC_OK;
+}
+
+extern "C" int lmpc_est_report(const lmpc_rbd_model* model, const lmpc_est_sensors* sensors, const lmpc_est_filter* filter,
+                               lmpc_rbd_state* state_est, lmpc_est_out* out) {
+    if (!model || !sensors || !filter) return LMPC_ERR_ARG;
+    report_robot(*model, *sensors, *filter, state_est, out);
+    return LMPC_OK;
+}
+
+extern "C" int lmpc_est_update(const lmpc_rbd_model* model, const lmpc_est_cfg* cfg, const lmpc_est_sensors* sensors,
+                               lmpc_est_filter* filter, lmpc_rbd_state* state_est, lmpc_est_out* out) {
+    if (!model || !cfg || !sensors || !filter || !good_cfg(*cfg)) return LMPC_ERR_ARG;
+    update_robot(*model, *cfg, *sensors, *filter, state_est, out);
+    return LMPC_OK;
+}
+
+extern "C" int lmpc_est_feedback(const lmpc_sim_out* sim_out, const lmpc_est_out* out, lmpc_sim_out* shadow) {
+    if (!sim_out || !out || !shadow) return LMPC_ERR_ARG;
+    feedback_robot(*sim_out, *out, *shadow);
+    return LMPC_OK;
+}
+
+extern "C" int lmpc_est_sensors_from_plant_device(const lmpc_rbd_model* model, const lmpc_est_cfg* cfg,
+                                                  const lmpc_rbd_state* d_state, const lmpc_sim_out* d_sim_out, int batch,
+                                                  int32_t index0, uint32_t tick, const int32_t* d_gait,
+                                                  int64_t gait_stride, lmpc_est_sensors* d_sensors, void* stream) {
+    if (batch < 0 || (batch > 0 && (!model || !cfg || !d_state || !d_sim_out || !d_sensors || !good_sigmas(*cfg) ||
+                                    (d_gait && gait_stride < 1))))
+        return LMPC_ERR_ARG;
+    if (batch == 0) return LMPC_OK;
+    hipLaunchKernelGGL(lmpc_est_sensors_kernel, dim3((batch + ONE_THREADS - 1) / ONE_THREADS), dim3(ONE_THREADS), 0,
+                       (hipStream_t)stream, *model, *cfg, d_state, d_sim_out, batch, index0, tick, d_gait,
+                       (long long)gait_stride, d_sensors);
+    return launch_rc();
+}
+
+extern "C" int lmpc_est_init_device(const lmpc_rbd_model* model, const lmpc_est_cfg* cfg, const lmpc_est_sensors* d_sensors,
+                                    const double* d_pos0, int64_t pos0_stride, int batch, lmpc_est_filter* d_filter,
+                                    lmpc_rbd_state* d_state_est, lmpc_est_out* d_out, const lmpc_sim_out* d_sim_out,
+                                    lmpc_sim_out* d_shadow, void* stream) {
+    if (batch < 0 || (batch > 0 && (!model || !cfg || !d_sensors || !d_filter || (d_pos0 && pos0_stride < 3) ||
+                                    (d_shadow && !d_sim_out))))
+        return LMPC_ERR_ARG;
+    if (batch == 0) return LMPC_OK;
+    hipLaunchKernelGGL(lmpc_est_init_kernel, dim3((batch + ONE_THREADS - 1) / ONE_THREADS), dim3(ONE_THREADS), 0,
+                       (hipStream_t)stream, *model, *cfg, d_sensors, d_pos0, (long long)pos0_stride, batch, d_filter,
+                       d_state_est, d_out, d_sim_out, d_shadow);
+    return launch_rc();
+}
+
+extern "C" int lmpc_est_update_device(const lmpc_rbd_model* model, const lmpc_est_cfg* cfg, const lmpc_est_sensors* d_sensors,
+                                      int batch, lmpc_est_filter* d_filter, lmpc_rbd_state* d_state_est,
+                                      lmpc_est_out* d_out, const lmpc_sim_out* d_sim_out, lmpc_sim_out* d_shadow,
+                                      void* stream) {
+    if (batch < 0 || (batch > 0 && (!model || !cfg || !d_sensors || !d_filter || !good_cfg(*cfg) ||
+                                    (d_shadow && (!d_sim_out || d_shadow == d_sim_out)))))
+        return LMPC_ERR_ARG;
+    if (batch == 0) return LMPC_OK;
+    hipLaunchKernelGGL(lmpc_est_update_kernel, dim3((batch + BLOCK_ROBOTS - 1) / BLOCK_ROBOTS), dim3(BLOCK), 0,
+                       (hipStream_t)stream, *model, *cfg, d_sensors, batch, d_filter, d_state_est, d_out, d_sim_out,
+                       d_shadow);
+    return launch_rc();
+}

@@ -7,7 +7,11 @@
     HBM, asynchronous on a stream; the advance launch also expands the commands into the MPC context's record buffers;
   * `StackLoop` -- per MPC tick: advance, QP, targets, then `wbc_per_mpc` low-level ticks of `WbcPipeline.solve_device`
     and `lmpc_sim_step_device`, the plant's candidate contacts being `held | touch` of its previous step; one stream,
-    no host synchronisation and no allocation inside the loop.
+    no host synchronisation and no allocation inside the loop.  With `estimator=est.cfg()` the controllers no longer
+    see the plant's state: after every plant step the loop reads sensors off the plant (`est.sensors_from_plant_device`)
+    and runs the reference's Kalman filter (`est.update_device`); the advance and the WBC then read the estimated
+    state and a shadow `lmpc_sim_out` with the estimate's feet and contact flags, while the plant and the candidate
+    rule keep reading the true ones.
 
 What is restated from the reference and what is this library's choice (zero latency, the candidate rule, `touch` as
 the contact flag, the standing mode's foot targets, what a failed stage leaves): include/lmpc/lmpc_stack.h.  The
@@ -20,6 +24,7 @@ import ctypes
 import numpy as np
 
 from . import _native as N
+from . import est as E
 from . import sim as S
 from .hoqp import check_device_tensor
 from .rbd import STATE_BYTES, TARGET_BYTES, WbcPipeline, target as wbc_target
@@ -196,7 +201,10 @@ class StackLoop:
 
     def __init__(self, model: N.LmpcRbdModel, params: N.LmpcParams, horizon: int, max_batch: int,
                  rollout_cfg: N.LmpcRolloutCfg, sim_cfg: N.LmpcSimCfg, wbc_per_mpc: int, substeps: int = 1,
-                 template: N.LmpcWbcTarget = None, device: int = 0):
+                 template: N.LmpcWbcTarget = None, device: int = 0, estimator: N.LmpcEstCfg = None):
+        """estimator: an `lmpc_est_cfg` (est.cfg(dt=...)) closes the loop on the Kalman filter's estimate instead of the
+        plant's own state; its dt must be the low-level tick's, substeps * sim_cfg.dt.  None: the plant's state is the
+        feedback, exactly as without this option."""
         import torch
 
         if max_batch < 1:
@@ -220,6 +228,36 @@ class StackLoop:
         self.d_qp_iters = torch.zeros(self.max_batch, dtype=torch.int32, device=dev)
         self.d_target = torch.zeros((self.max_batch, TARGET_BYTES), dtype=torch.uint8, device=dev)
         self.d_candidates = torch.zeros((self.max_batch, 4), dtype=torch.int32, device=dev)
+        self.estimator = estimator
+        if estimator is not None:
+            if not abs(estimator.dt - self.substeps * sim_cfg.dt) <= 1e-12:
+                raise ValueError(f"estimator dt {estimator.dt} is not the low-level tick's, substeps {self.substeps} x sim "
+                                 f"dt {sim_cfg.dt}")
+
+            def buf(width):
+                return torch.zeros((self.max_batch, width), dtype=torch.uint8, device=dev)
+
+            self.d_sensors, self.d_filter = buf(E.SENSORS_BYTES), buf(E.FILTER_BYTES)
+            self.d_state_est, self.d_est_out, self.d_shadow = buf(STATE_BYTES), buf(E.OUT_BYTES), buf(S.OUT_BYTES)
+            self.reset_estimator()
+
+    def reset_estimator(self):
+        """The next `run_device` initialises every robot's filter anew (it does so by itself on the first call, and
+        when the batch size changes)."""
+        self._est_batch, self._est_tick = 0, 0
+
+    def _init_estimator(self, d_robots, d_state, d_sim_out, B, s):
+        """Filters from the robots' current sensors, with pos0 = the TRUE position: this library's choice -- the
+        reference's default (0, 0, 0.09) is the height of a robot lying on the ground, and these robots start
+        standing.  Also leaves the first estimated state and shadow block for the first advance."""
+        import torch
+
+        E.sensors_from_plant_device(self.model, self.estimator, d_state, d_sim_out, self.d_sensors[:B], 0, 0,
+                                    E.gait_view(d_robots), s)
+        E.init_device(self.model, self.estimator, self.d_sensors[:B], self.d_filter[:B],
+                      d_state.view(torch.float64)[:, 3:6], self.d_state_est[:B], self.d_est_out[:B], d_sim_out,
+                      self.d_shadow[:B], s)
+        self._est_batch, self._est_tick = B, 0
 
     def close(self):
         self.pipeline.close()
@@ -235,7 +273,11 @@ class StackLoop:
         `qp_iters` int32 [T][B], `target` uint8 [T][B][352].  Per low-level tick k = t * wbc_per_mpc + i: `states`
         uint8 [K][B][288] and `out` uint8 [K][B][472] (after the plant step; `held`, `touch` int32 [K][B][4] and
         `sim_status` int32 [K][B] are views of it), `tau` float64 [K][B][12], `candidates` int32 [K][B][4],
-        `wbc_status` int32 [K][B]."""
+        `wbc_status` int32 [K][B].  With an estimator also, per low-level tick: `sensors` uint8 [K][B][296], `state_est`
+        uint8 [K][B][288], `filter` uint8 [K][B][2744] (x and P after the update; est.filter_view), `est_out` uint8
+        [K][B][312] (`est_status` int32 [K][B] is a view of it), `shadow` uint8 [K][B][472]; and `filter0`,
+        `state_est0`, `shadow0` [B][...]: the estimator as this call found it.  `states` and `out` stay the TRUE ones;
+        the noise of low-level tick n (counted from the filters' initialisation, from 1) is keyed (seed, robot, n)."""
         import torch
 
         B = int(d_robots.shape[0]) if d_robots.dim() >= 1 else -1
@@ -251,6 +293,12 @@ class StackLoop:
         T, W = int(mpc_ticks), self.wbc_per_mpc
         d_grf, d_qst, d_qit = self.d_grf[:B], self.d_qp_status[:B], self.d_qp_iters[:B]
         d_target, d_cand = self.d_target[:B], self.d_candidates[:B]
+        est = self.estimator
+        d_fb_state, d_fb_out = d_state, d_sim_out  # what the advance and the WBC read
+        if est is not None:
+            d_sens, d_filt, d_eout = self.d_sensors[:B], self.d_filter[:B], self.d_est_out[:B]
+            d_fb_state, d_fb_out = self.d_state_est[:B], self.d_shadow[:B]
+            d_gait = E.gait_view(d_robots)
         logs = None
         if log:
             K = T * W
@@ -264,9 +312,19 @@ class StackLoop:
                         tau=torch.empty((K, B, 12), dtype=torch.float64, device=dev),
                         candidates=torch.empty((K, B, 4), dtype=torch.int32, device=dev),
                         wbc_status=torch.empty((K, B), dtype=torch.int32, device=dev))
+            if est is not None:
+                for name, width in (("sensors", E.SENSORS_BYTES), ("state_est", STATE_BYTES), ("filter", E.FILTER_BYTES),
+                                    ("est_out", E.OUT_BYTES), ("shadow", S.OUT_BYTES)):
+                    logs[name] = torch.empty((K, B, width), dtype=torch.uint8, device=dev)
         with torch.cuda.stream(s):
+            if est is not None:
+                if self._est_batch != B:
+                    self._init_estimator(d_robots, d_state, d_sim_out, B, s)
+                if log:
+                    logs["filter0"], logs["state_est0"] = d_filt.clone(), d_fb_state.clone()
+                    logs["shadow0"] = d_fb_out.clone()
             for t in range(T):
-                advance_device(self.solver, self.rollout_cfg, d_robots, d_state, d_sim_out, s)
+                advance_device(self.solver, self.rollout_cfg, d_robots, d_fb_state, d_fb_out, s)
                 solve_device(self.solver, d_grf, d_qst, d_qit, s)
                 targets_device(d_robots, d_grf, self.template, d_target, s)
                 if log:
@@ -277,9 +335,13 @@ class StackLoop:
                     logs["target"][t].copy_(d_target)
                 for i in range(W):
                     candidates_device(d_sim_out, d_cand, s)
-                    d_x, d_wst = self.pipeline.solve_device(d_state, d_target, s)
+                    d_x, d_wst = self.pipeline.solve_device(d_fb_state, d_target, s)
                     d_tau = d_x[:, S.TAU_OFFSET:S.TAU_OFFSET + 12]
                     S.step_device(self.model, self.sim_cfg, d_state, d_tau, d_cand, d_state, d_sim_out, self.substeps, s)
+                    if est is not None:
+                        self._est_tick += 1
+                        E.sensors_from_plant_device(self.model, est, d_state, d_sim_out, d_sens, self._est_tick, 0, d_gait, s)
+                        E.update_device(self.model, est, d_sens, d_filt, d_fb_state, d_eout, d_sim_out, d_fb_out, s)
                     if log:
                         k = t * W + i
                         logs["states"][k].copy_(d_state)
@@ -287,8 +349,16 @@ class StackLoop:
                         logs["tau"][k].copy_(d_tau)
                         logs["candidates"][k].copy_(d_cand)
                         logs["wbc_status"][k].copy_(d_wst)
+                        if est is not None:
+                            logs["sensors"][k].copy_(d_sens)
+                            logs["state_est"][k].copy_(d_fb_state)
+                            logs["filter"][k].copy_(d_filt)
+                            logs["est_out"][k].copy_(d_eout)
+                            logs["shadow"][k].copy_(d_fb_out)
         if log:
             flags = logs["out"].view(torch.int32)[..., S.OUT_BYTES // 4 - 10:]  # held (4), touch (4), status, reserved
             logs["cmd"] = logs["robots"][..., :N.COMMAND_BYTES]
             logs["held"], logs["touch"], logs["sim_status"] = flags[..., 0:4], flags[..., 4:8], flags[..., 8]
+            if est is not None:
+                logs["est_status"] = logs["est_out"].view(torch.int32)[..., E.OUT_BYTES // 4 - 2]
         return logs

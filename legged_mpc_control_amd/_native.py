@@ -89,6 +89,13 @@ EST_SYMBOLS = (
     "lmpc_est_feedback", "lmpc_est_sensors_from_plant_device", "lmpc_est_init_device", "lmpc_est_update_device",
 )
 EST_ABI_VERSION = 1
+# include/lmpc/lmpc_contact.h: the frictional contact model of the plant
+CONTACT_SYMBOLS = (
+    "lmpc_contact_abi_version", "lmpc_contact_cfg_size", "lmpc_contact_out_size", "lmpc_contact_cfg_default",
+    "lmpc_contact_work_bytes", "lmpc_contact_solve", "lmpc_contact_step", "lmpc_contact_solve_device",
+    "lmpc_contact_step_device",
+)
+CONTACT_ABI_VERSION = 1
 
 
 class LmpcParams(ctypes.Structure):
@@ -259,6 +266,23 @@ class LmpcSimOut(ctypes.Structure):
         ("qdd", ctypes.c_double * 18), ("force", ctypes.c_double * 12), ("foot_pos", ctypes.c_double * 12),
         ("foot_vel", ctypes.c_double * 12), ("held", ctypes.c_int32 * 4), ("touch", ctypes.c_int32 * 4),
         ("status", ctypes.c_int32), ("reserved", ctypes.c_int32),
+    ]
+
+
+class LmpcContactCfg(ctypes.Structure):
+    _fields_ = [
+        ("dt", ctypes.c_double), ("ground_z", ctypes.c_double), ("mu", ctypes.c_double),
+        ("recover_speed", ctypes.c_double), ("force_threshold", ctypes.c_double), ("tol_p", ctypes.c_double),
+        ("tol_d", ctypes.c_double), ("use_gap", ctypes.c_int32), ("touch_rule", ctypes.c_int32),
+        ("max_sweeps", ctypes.c_int32), ("max_polish", ctypes.c_int32),
+    ]
+
+
+class LmpcContactOut(ctypes.Structure):
+    _fields_ = [
+        ("w", ctypes.c_double * 12), ("gap", ctypes.c_double * 4), ("res_primal", ctypes.c_double),
+        ("res_dual", ctypes.c_double), ("mode", ctypes.c_int32 * 4), ("sweeps", ctypes.c_int32),
+        ("polish", ctypes.c_int32), ("status", ctypes.c_int32), ("reserved", ctypes.c_int32),
     ]
 
 
@@ -568,6 +592,27 @@ def lib():
         if L.lmpc_est_abi_version() != EST_ABI_VERSION or est_sizes != est_mirrors:
             raise NativeLibraryError(f"{path}: lmpc_est.h ABI {L.lmpc_est_abi_version()} with struct sizes {est_sizes}, "
                                      f"this binding is ABI {EST_ABI_VERSION} with {est_mirrors}")
+        ccp, cop = ctypes.POINTER(LmpcContactCfg), ctypes.POINTER(LmpcContactOut)
+        for name in ("lmpc_contact_abi_version", "lmpc_contact_cfg_size", "lmpc_contact_out_size"):
+            getattr(L, name).restype = ctypes.c_int
+        L.lmpc_contact_cfg_default.argtypes = [ccp]
+        L.lmpc_contact_cfg_default.restype = None
+        L.lmpc_contact_work_bytes.argtypes = [ctypes.c_int]
+        L.lmpc_contact_work_bytes.restype = ctypes.c_size_t
+        L.lmpc_contact_solve.argtypes = [ccp, dp, dp, i32p, dp, cop]
+        L.lmpc_contact_solve.restype = ctypes.c_int
+        L.lmpc_contact_step.argtypes = [mp, ccp, sp, dp, i32p, sp, sop, cop]
+        L.lmpc_contact_step.restype = ctypes.c_int
+        L.lmpc_contact_solve_device.argtypes = [ccp, vp, vp, vp, ctypes.c_int, vp, vp, vp]
+        L.lmpc_contact_solve_device.restype = ctypes.c_int
+        L.lmpc_contact_step_device.argtypes = [mp, ccp, vp, vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int,
+                                               ctypes.c_int, vp, vp, vp, vp, ctypes.c_size_t, vp]
+        L.lmpc_contact_step_device.restype = ctypes.c_int
+        contact_sizes = (L.lmpc_contact_cfg_size(), L.lmpc_contact_out_size())
+        contact_mirrors = (ctypes.sizeof(LmpcContactCfg), ctypes.sizeof(LmpcContactOut))
+        if L.lmpc_contact_abi_version() != CONTACT_ABI_VERSION or contact_sizes != contact_mirrors:
+            raise NativeLibraryError(f"{path}: lmpc_contact.h ABI {L.lmpc_contact_abi_version()} with struct sizes "
+                                     f"{contact_sizes}, this binding is ABI {CONTACT_ABI_VERSION} with {contact_mirrors}")
         if L.lmpc_rollout_abi_version() != ROLLOUT_ABI_VERSION or L.lmpc_robot_size() != ROBOT_BYTES:
             raise NativeLibraryError(f"{path}: lmpc_rollout.h ABI {L.lmpc_rollout_abi_version()} / lmpc_robot of "
                                      f"{L.lmpc_robot_size()} B, this binding is ABI {ROLLOUT_ABI_VERSION} / {ROBOT_BYTES} B")

@@ -1,0 +1,484 @@
+// lmpc_contact.hip -- the frictional contact model of include/lmpc/lmpc_contact.h: the bare pyramid problem and the
+// plant step that solves it, on the host (one robot) and on the device (a batch, four lanes per robot).
+//
+// The arithmetic is lmpc_sim_common.h's (the elimination up to K = J M^-1 J') and lmpc_contact_common.h's (modes, one
+// foot's problem, the reduced blocks, the certificate), compiled for both sides.  Device mapping, as lmpc_sim.hip's:
+// lane 4 r + l of a wavefront owns foot l of the wavefront's r-th robot and holds block row l of K (all four blocks:
+// the Gauss-Seidel sweep needs the whole row).  The sweep is serial over the quad: at step k every lane gathers the
+// four P by quad shuffles and solves its own foot's problem, and lane k's answer is the one kept.  The polish is
+// lmpc_sim.hip's block Cholesky over the quad on the blocks reduced to the modes' bases.  Every lane runs every phase;
+// the loop's exit is wavefront-uniform, and a quad that is done is frozen: its result does not depend on how long its
+// neighbours take.  The fused step kernel keeps the state in registers across substeps; no LDS, no workspace.  It
+// spills (157 VGPRs), so the step also exists in three launches around the bare solve kernel, none of which spills, on
+// a caller's workspace; measured, the fused kernel is still the faster one.
+#include <hip/hip_runtime.h>
+
+#include "lmpc/lmpc_contact.h"
+#include "lmpc_contact_common.h"
+#include "lmpc_quad_device.h"
+
+static_assert(sizeof(lmpc_contact_cfg) == 72, "lmpc_contact_cfg layout (legged_mpc_control_amd/_native.py)");
+static_assert(sizeof(lmpc_contact_out) == 176, "lmpc_contact_out layout");
+static_assert(sizeof(lmpc_sim_out) == 472, "lmpc_sim_out layout");
+
+namespace lmpc_contact {
+namespace {
+
+constexpr int BLOCK = 64;                // one wavefront per block, as lmpc_sim.hip
+constexpr int BLOCK_ROBOTS = BLOCK / 4;  // one quad of lanes per robot
+
+#if defined(__HIPCC__)
+__device__ inline double quad_max(double v) {
+    return fmax(fmax(quad_get(v, 0), quad_get(v, 1)), fmax(quad_get(v, 2), quad_get(v, 3)));
+}
+
+// ---- the quad's solver ----------------------------------------------------------------------------------------------
+// lmpc_contact_common.h's solve_modes(): K[k] = K_Lk, KLL = K_LL.  ok: quad-uniform, false on a non-positive pivot.
+__device__ inline V3 quad_polish(const Blk K[4], const Blk& KLL, const V3& c, int mode, double mu, int L, bool& ok) {
+    const Basis bL = mode_basis(mode, mu);
+    Blk B[4], Dg;  // B[k] = the reduced K_Lk for k < L, Dg = the reduced K_LL
+    reduce_blk(KLL, bL, bL, true, Dg);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) reduce_blk(K[k], bL, mode_basis(__shfl(mode, k, 4), mu), false, B[k]);
+    const V3 floor = blk_floor(Dg);
+    Chol3 Ld;
+    ok = true;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const bool okk = chol3(Dg.a, floor, Ld);
+        ok = ok && quad_get_flag(okk, k);
+        const Chol3 Lkk{quad_get(Ld.l00, k), quad_get(Ld.l10, k), quad_get(Ld.l11, k),
+                        quad_get(Ld.l20, k), quad_get(Ld.l21, k), quad_get(Ld.l22, k)};
+        blk_trsm(B[k], Lkk);
+#pragma unroll
+        for (int j = k + 1; j < 4; ++j) {
+            Blk Ljk, X = B[j];
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int q = 0; q < 3; ++q) Ljk.a[i][q] = quad_get(B[k].a[i][q], j);
+            blk_pick(X, L == j, Dg);
+            blk_update(X, B[k], Ljk);
+            blk_pick(Dg, L == j, X);
+            blk_pick(B[j], L != j, X);
+        }
+    }
+    V3 t = reduce_rhs(bL, c);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {  // L y = t
+        const V3 y = chol3_fwd(Ld, t);
+        const V3 yk = quad_get(y, k);
+        const V3 lower = sub(t, mul3(B[k].a, yk));
+        t = sel(L == k, y, sel(L > k, lower, t));
+    }
+    V3 y = v3(0.0, 0.0, 0.0);
+#pragma unroll
+    for (int k = 3; k >= 0; --k) {  // L' y = t
+        const V3 u = mul3t(B[k].a, y);
+        V3 a = t;
+#pragma unroll
+        for (int m = k + 1; m < 4; ++m) a = sub(a, quad_get(u, m));
+        const V3 yk = chol3_bwd(Ld, a);
+        y = sel(L == k, yk, y);
+    }
+    return sel(mode < MODE_APEX, basis_apply(bL, y), v3(0.0, 0.0, 0.0));
+}
+
+// lmpc_contact_common.h's certify(): this foot's w, the quad's residuals
+__device__ inline void quad_certify(const Blk K[4], const V3& c, bool in, int mode, const V3& P, double mu, V3& w,
+                                    double& rp, double& rd) {
+    const V3 Pall[4] = {quad_get(P, 0), quad_get(P, 1), quad_get(P, 2), quad_get(P, 3)};
+    w = sel(in, row_sum(K, Pall, c, -1), v3(0.0, 0.0, 0.0));
+    double pv, dv;
+    foot_cert(mode, P, w, mu, pv, dv);
+    const double s = fmax(1.0, quad_max(foot_scale(P, c, in)));
+    rp = quad_max(pv) / s, rd = quad_max(dv) / s;
+}
+
+struct LaneSol {
+    V3 P, w;
+    int mode, sweeps, polish;
+    double res_p, res_d;
+    bool bad, certified;  // quad-uniform
+};
+// lmpc_contact_common.h's solve_quad()
+__device__ inline void quad_solve(const Blk K[4], const V3& c, bool in, int L, const Caps& cp, LaneSol& s) {
+    Blk KLL = K[0];
+    blk_pick(KLL, L == 1, K[1]);
+    blk_pick(KLL, L == 2, K[2]);
+    blk_pick(KLL, L == 3, K[3]);
+    V3 P = v3(0.0, 0.0, 0.0);
+    int mode = start_mode(in, cp.max_polish > 0), sweeps = 0, polish = 0;
+    bool done = false, bad = false;
+    for (int it = 0; it <= cp.max_sweeps; ++it) {
+        if (!__any(!done)) break;
+        V3 Pn = P;
+        int mn = mode;
+        if (it > 0) {
+#pragma unroll 1
+            for (int k = 0; k < 4; ++k) {
+                const V3 Pall[4] = {quad_get(Pn, 0), quad_get(Pn, 1), quad_get(Pn, 2), quad_get(Pn, 3)};
+                V3 Ps;
+                int ms;
+                foot_subqp(KLL, row_sum(K, Pall, c, L), cp.mu, Ps, ms);
+                const bool adopt = in && L == k;
+                Pn = sel(adopt, Ps, Pn), mn = adopt ? ms : mn;
+            }
+        }
+        const bool use_p = polish < cp.max_polish;
+        V3 cand = Pn;
+        bool okp = true;
+        if (__any(use_p && !done)) {
+            const V3 Pp = quad_polish(K, KLL, c, mn, cp.mu, L, okp);
+            cand = sel(use_p, Pp, Pn), okp = okp || !use_p;
+        }
+        V3 w;
+        double rp, rd;
+        quad_certify(K, c, in, mn, cand, cp.mu, w, rp, rd);
+        const bool pfeas = rp <= cp.tol_p, verified = pfeas && rd <= cp.tol_d;
+        // a quad that is done keeps what it has: repeating it changes nothing
+        const bool live = !done;
+        sweeps += (live && it > 0) ? 1 : 0, polish += (live && use_p) ? 1 : 0;
+        bad = bad || (live && !okp);
+        P = sel(live, sel(pfeas, cand, Pn), P);
+        mode = !live ? mode : ((it == 0 && !pfeas) ? start_mode(in, false) : mn);
+        done = done || verified || bad;
+    }
+    s.P = P, s.mode = mode, s.sweeps = sweeps, s.polish = polish, s.bad = bad;
+    quad_certify(K, c, in, mode, P, cp.mu, s.w, s.res_p, s.res_d);
+    s.certified = s.res_p <= cp.tol_p && s.res_d <= cp.tol_d;
+}
+
+// ---- the bare problem ----------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(BLOCK)
+    lmpc_contact_solve_kernel(const double* __restrict__ Ks, const double* __restrict__ cs,
+                              const int32_t* __restrict__ masks, int batch, Caps cp, double* __restrict__ Ps,
+                              lmpc_contact_out* outs) {
+    const int robot = blockIdx.x * BLOCK_ROBOTS + (threadIdx.x >> 2), L = threadIdx.x & 3;
+    // a quad past the batch computes the last problem again and stores nothing: the shuffles below stay uniform
+    const bool active = robot < batch;
+    const long long r = active ? robot : batch - 1;
+    Blk K[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) K[k].a[i][j] = Ks[r * 144 + (3 * L + i) * 12 + 3 * k + j];
+    const V3 c = v3(cs[r * 12 + 3 * L], cs[r * 12 + 3 * L + 1], cs[r * 12 + 3 * L + 2]);
+    const bool in = masks[r * 4 + L] != 0;
+    LaneSol s;
+    quad_solve(K, c, in, L, cp, s);
+    const bool failed = quad_any(s.bad || !finite(s.P) || !finite(s.w));
+    if (!active) return;
+    const V3 P = sel(failed, v3(0.0, 0.0, 0.0), s.P);
+    Ps[r * 12 + 3 * L] = P.x, Ps[r * 12 + 3 * L + 1] = P.y, Ps[r * 12 + 3 * L + 2] = P.z;
+    if (outs) {
+        lmpc_contact_out& o = outs[r];
+        const V3 w = sel(failed, v3(0.0, 0.0, 0.0), s.w);
+        o.w[3 * L] = w.x, o.w[3 * L + 1] = w.y, o.w[3 * L + 2] = w.z;
+        o.gap[L] = 0.0;
+        o.mode[L] = failed ? 0 : s.mode;
+        if (L == 0) o.res_primal = failed ? 0.0 : s.res_p, o.sweeps = failed ? 0 : s.sweeps, o.reserved = 0;
+        if (L == 1) o.res_dual = failed ? 0.0 : s.res_d, o.polish = failed ? 0 : s.polish;
+        if (L == 2) o.status = failed ? 1 : (s.certified ? 0 : 2);
+    }
+}
+
+// ---- the plant step (lmpc_sim.hip's kernel with the contact problem in the place of the unilateral rule) ------------
+struct StepArgs {
+    double dt, ground_z, recover_speed, force_threshold;
+    int use_gap, touch_rule;
+    Caps caps;
+};
+
+// The caller's workspace of the three-launch form, per robot: K (144 doubles), c (12), P (12), the solve's
+// lmpc_contact_out, the mask (4 int32) and the flag "a substep of this step was not certified" (int32, padded to 8).
+constexpr size_t WORK_PER_ROBOT = (144 + 12 + 12) * sizeof(double) + sizeof(lmpc_contact_out) + 4 * sizeof(int32_t) + 8;
+struct Work {
+    double *K, *c, *P;
+    lmpc_contact_out* out;
+    int32_t *mask, *sticky;
+};
+inline Work work_of(void* d_work, int batch) {
+    Work w;
+    char* p = static_cast<char*>(d_work);
+    w.K = reinterpret_cast<double*>(p), p += (size_t)batch * 144 * sizeof(double);
+    w.c = reinterpret_cast<double*>(p), p += (size_t)batch * 12 * sizeof(double);
+    w.P = reinterpret_cast<double*>(p), p += (size_t)batch * 12 * sizeof(double);
+    w.out = reinterpret_cast<lmpc_contact_out*>(p), p += (size_t)batch * sizeof(lmpc_contact_out);
+    w.mask = reinterpret_cast<int32_t*>(p), p += (size_t)batch * 4 * sizeof(int32_t);
+    w.sticky = reinterpret_cast<int32_t*>(p);
+    return w;
+}
+
+// FORM 0: the fused step (everything in one launch, substeps with the state in registers).  The three-launch form
+// runs the same arithmetic around lmpc_contact_solve_kernel: FORM 1 builds K and c and stores them (one substep, no
+// state written), FORM 2 builds the elimination again, takes P and the solve's report from the workspace and
+// back-substitutes (one substep; `first` = 0 carries the not-certified flag over from the substep before).
+constexpr int FUSED = 0, TERMS = 1, APPLY = 2;
+template <int FORM>
+__global__ void __launch_bounds__(BLOCK)
+    lmpc_contact_step_kernel(const lmpc_rbd_model md, const lmpc_rbd_state* states, const double* __restrict__ taus,
+                             long long tau_stride, const int32_t* __restrict__ masks, long long mask_stride, int batch,
+                             int substeps, const StepArgs a, lmpc_rbd_state* nexts, lmpc_sim_out* outs,
+                             lmpc_contact_out* couts, const Work wk, int first) {
+    const int robot = blockIdx.x * BLOCK_ROBOTS + (threadIdx.x >> 2), L = threadIdx.x & 3;
+    // a quad past the batch computes the last robot again and stores nothing: the shuffles below stay uniform
+    const bool active = robot < batch;
+    const int r = active ? robot : batch - 1;
+    const double dt = a.dt;
+
+    // the base's state, and the lane's own joints in slot 0
+    lmpc_rbd_state ls;
+    {
+        const lmpc_rbd_state& st = states[r];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            ls.euler[i] = st.euler[i], ls.pos[i] = st.pos[i], ls.omega[i] = st.omega[i], ls.lin_vel[i] = st.lin_vel[i];
+            ls.joint_pos[i] = st.joint_pos[3 * L + i], ls.joint_vel[i] = st.joint_vel[3 * L + i];
+        }
+    }
+    const double* tp = taus + (long long)r * tau_stride + 3 * L;
+    const double tau3[3] = {tp[0], tp[1], tp[2]};
+    const bool in = masks[(long long)r * mask_stride + L] != 0;
+
+    bool failed = false;  // quad-uniform; once set the state is frozen
+    // quad-uniform: some substep's answer did not pass the certificate (status 2 unless the step fails)
+    bool uncertified = FORM == APPLY && first == 0 && wk.sticky[r] != 0;
+
+    for (int step = 0; step < substeps; ++step) {
+        // the leg's 42 doubles of the model are loaded anew in every substep (lmpc_sim.hip: hoisted, they spill)
+        int Ll = L;
+        asm volatile("" : "+v"(Ll));
+        lmpc_rbd_model lm;
+        lane_model(md, Ll, lm);
+        const BaseKin bk = base_kin(ls);
+        LegOut g;
+        leg_pass(lm, ls, bk, 0, g);
+        BaseOut base;
+        base_pass(bk, total_part(trunk_part(lm, bk), quad_get(g.sum, 0), quad_get(g.sum, 1), quad_get(g.sum, 2),
+                                 quad_get(g.sum, 3)), base);
+        V3 rl, c0;
+        leg_rhs(g, tau3, dt, true, rl, c0);
+        LegRed rd;
+        leg_reduce(g, rl, c0, rd);
+        bool bad = !rd.okm;
+        double e[NC + 6], yb[6];
+        base_entries(base, dt, e);
+#pragma unroll
+        for (int n = 0; n < NC + 6; ++n)
+            e[n] = minus4(e[n], quad_get(rd.Cs[n], 0), quad_get(rd.Cs[n], 1), quad_get(rd.Cs[n], 2), quad_get(rd.Cs[n], 3));
+        Chol6 Ls;
+        bad = !base_factor(e, Ls, yb) || bad;
+        LegRows w;
+        leg_rows(rd, Ls, yb, w);
+        Blk K[4];  // K[k] = K_Lk, the whole block row
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            double Zk[3][6];
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 6; ++j) Zk[i][j] = quad_get(w.Z[i][j], k);
+            blk_of(w.Z, Zk, rd.A, L == k, K[k]);
+        }
+
+        // the contact problem
+        const double gap = (ls.pos[2] + g.foot.z) - a.ground_z;
+        const V3 c = contact_c(w.rhs, gap, a.use_gap != 0, a.recover_speed, dt);
+        if (FORM == TERMS) {
+            if (active) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+#pragma unroll
+                    for (int i = 0; i < 3; ++i)
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) wk.K[(long long)r * 144 + (3 * L + i) * 12 + 3 * k + j] = K[k].a[i][j];
+                double* cw = wk.c + (long long)r * 12 + 3 * L;
+                cw[0] = c.x, cw[1] = c.y, cw[2] = c.z;
+                wk.mask[(long long)r * 4 + L] = in ? 1 : 0;
+            }
+            return;
+        }
+        LaneSol s;
+        if (FORM == APPLY) {  // what lmpc_contact_solve_kernel left: P and w are zero and status is 1 if it failed
+            const lmpc_contact_out& so = wk.out[r];
+            const double* Pw = wk.P + (long long)r * 12 + 3 * L;
+            s.P = v3(Pw[0], Pw[1], Pw[2]), s.w = v3(so.w[3 * L], so.w[3 * L + 1], so.w[3 * L + 2]);
+            s.mode = so.mode[L], s.sweeps = so.sweeps, s.polish = so.polish;
+            s.res_p = so.res_primal, s.res_d = so.res_dual;
+            s.bad = so.status == 1, s.certified = so.status == 0;
+        } else {
+            quad_solve(K, c, in, L, a.caps, s);
+        }
+        bad = bad || s.bad;
+        uncertified = uncertified || !s.certified;
+        const V3 P = s.P;
+        // back-substitution
+        double zp[6], t6[6], xb[6];
+        leg_zp(w, P, zp);
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+            t6[i] = plus4(yb[i], quad_get(zp[i], 0), quad_get(zp[i], 1), quad_get(zp[i], 2), quad_get(zp[i], 3));
+        base_back(Ls, t6, xb);
+        const V3 xl = leg_back(g, rd, rl, xb, P);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) bad = bad || !finite(xb[i]);
+        bad = bad || !finite(xl) || !finite(P) || !finite(s.w);
+        failed = failed || quad_any(bad);
+        // what the last substep reports (a failed robot: zeros); nothing of it is carried through the loop
+        double oq[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        V3 oqdd = v3(0.0, 0.0, 0.0), oforce = oqdd, ofp = oqdd, ofv = oqdd;
+        int otouch = 0;
+        if (!failed) {
+            const V3 pos = v3(ls.pos[0], ls.pos[1], ls.pos[2]);
+            BaseNext bn;
+            base_advance(bk, v3(ls.euler[0], ls.euler[1], ls.euler[2]), pos, xb, dt, bn);
+            LegNext ln;
+            leg_advance(g, v3(ls.joint_pos[0], ls.joint_pos[1], ls.joint_pos[2]),
+                        v3(ls.joint_vel[0], ls.joint_vel[1], ls.joint_vel[2]), xl, P, dt, bn, pos, ln);
+            ls.euler[0] = bn.euler.x, ls.euler[1] = bn.euler.y, ls.euler[2] = bn.euler.z;
+            ls.pos[0] = bn.pos.x, ls.pos[1] = bn.pos.y, ls.pos[2] = bn.pos.z;
+            ls.omega[0] = bn.omega.x, ls.omega[1] = bn.omega.y, ls.omega[2] = bn.omega.z;
+            ls.lin_vel[0] = bn.vlin.x, ls.lin_vel[1] = bn.vlin.y, ls.lin_vel[2] = bn.vlin.z;
+            ls.joint_pos[0] = ln.jp.x, ls.joint_pos[1] = ln.jp.y, ls.joint_pos[2] = ln.jp.z;
+            ls.joint_vel[0] = ln.jv.x, ls.joint_vel[1] = ln.jv.y, ls.joint_vel[2] = ln.jv.z;
+#pragma unroll
+            for (int i = 0; i < 6; ++i) oq[i] = bn.qdd[i];
+            oqdd = ln.qdd, oforce = ln.force, ofp = ln.foot_pos, ofv = ln.foot_vel;
+            otouch = touch_flag(a.touch_rule, ln.foot_pos.z, a.ground_z, ln.force, a.force_threshold);
+        }
+        if (step == substeps - 1) {
+            const int status = failed ? 1 : (uncertified ? 2 : 0);
+            if (FORM == APPLY && active && L == 0) wk.sticky[r] = uncertified ? 1 : 0;
+            if (outs) {
+                lmpc_sim_out& o = outs[r];
+                quad_store<6>(o.qdd, oq, L, active);
+                if (active) {
+                    o.qdd[6 + 3 * L] = oqdd.x, o.qdd[7 + 3 * L] = oqdd.y, o.qdd[8 + 3 * L] = oqdd.z;
+                    o.force[3 * L] = oforce.x, o.force[3 * L + 1] = oforce.y, o.force[3 * L + 2] = oforce.z;
+                    o.foot_pos[3 * L] = ofp.x, o.foot_pos[3 * L + 1] = ofp.y, o.foot_pos[3 * L + 2] = ofp.z;
+                    o.foot_vel[3 * L] = ofv.x, o.foot_vel[3 * L + 1] = ofv.y, o.foot_vel[3 * L + 2] = ofv.z;
+                    o.held[L] = (!failed && P.z > 0.0) ? 1 : 0;
+                    o.touch[L] = otouch;
+                    if (L == 0) o.status = status;
+                    if (L == 1) o.reserved = 0;
+                }
+            }
+            if (couts && active) {
+                lmpc_contact_out& o = couts[r];
+                const V3 ww = sel(failed, v3(0.0, 0.0, 0.0), s.w);
+                o.w[3 * L] = ww.x, o.w[3 * L + 1] = ww.y, o.w[3 * L + 2] = ww.z;
+                o.gap[L] = failed ? 0.0 : gap;
+                o.mode[L] = failed ? 0 : s.mode;
+                if (L == 0) o.res_primal = failed ? 0.0 : s.res_p, o.sweeps = failed ? 0 : s.sweeps, o.reserved = 0;
+                if (L == 1) o.res_dual = failed ? 0.0 : s.res_d, o.polish = failed ? 0 : s.polish;
+                if (L == 2) o.status = status;
+            }
+        }
+    }
+
+    lmpc_rbd_state& n = nexts[r];
+    const double q6[6] = {ls.euler[0], ls.euler[1], ls.euler[2], ls.pos[0], ls.pos[1], ls.pos[2]};
+    const double v6[6] = {ls.omega[0], ls.omega[1], ls.omega[2], ls.lin_vel[0], ls.lin_vel[1], ls.lin_vel[2]};
+    double* nd = reinterpret_cast<double*>(&n);  // 36 doubles: euler, pos, joint_pos, omega, lin_vel, joint_vel
+    quad_store<6>(nd, q6, L, active);
+    quad_store<6>(nd + 18, v6, L, active);
+    if (active) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) n.joint_pos[3 * L + i] = ls.joint_pos[i], n.joint_vel[3 * L + i] = ls.joint_vel[i];
+    }
+}
+#endif
+
+}  // namespace
+}  // namespace lmpc_contact
+
+using namespace lmpc_contact;
+
+extern "C" int lmpc_contact_abi_version(void) { return LMPC_CONTACT_ABI_VERSION; }
+extern "C" int lmpc_contact_cfg_size(void) { return (int)sizeof(lmpc_contact_cfg); }
+extern "C" int lmpc_contact_out_size(void) { return (int)sizeof(lmpc_contact_out); }
+extern "C" size_t lmpc_contact_work_bytes(int batch) { return batch > 0 ? (size_t)batch * WORK_PER_ROBOT : 0; }
+
+extern "C" void lmpc_contact_cfg_default(lmpc_contact_cfg* cfg) {
+    if (!cfg) return;
+    *cfg = lmpc_contact_cfg{};
+    cfg->dt = 0.002;
+    cfg->ground_z = 0.0;
+    cfg->mu = 0.6;
+    cfg->recover_speed = 0.0;
+    cfg->force_threshold = 50.0;
+    cfg->tol_p = 1e-9;
+    cfg->tol_d = 1e-9;
+    cfg->use_gap = 1;
+    cfg->touch_rule = 0;
+    cfg->max_sweeps = 16;
+    cfg->max_polish = 8;
+}
+
+extern "C" int lmpc_contact_solve(const lmpc_contact_cfg* cfg, const double* K, const double* c, const int32_t* mask,
+                                  double* P, lmpc_contact_out* out) {
+    if (!cfg || !K || !c || !mask || !P || !out || !good_solver_cfg(*cfg)) return LMPC_ERR_ARG;
+    solve_bare(*cfg, K, c, mask, P, *out);
+    return LMPC_OK;
+}
+
+extern "C" int lmpc_contact_step(const lmpc_rbd_model* model, const lmpc_contact_cfg* cfg, const lmpc_rbd_state* state,
+                                 const double* tau, const int32_t* mask, lmpc_rbd_state* next_state, lmpc_sim_out* out,
+                                 lmpc_contact_out* cout) {
+    if (!model || !cfg || !state || !tau || !mask || !next_state || !out || !good_step_cfg(*cfg)) return LMPC_ERR_ARG;
+    step_robot(*model, *cfg, *state, tau, mask, next_state, *out, cout);
+    return LMPC_OK;
+}
+
+extern "C" int lmpc_contact_solve_device(const lmpc_contact_cfg* cfg, const double* d_K, const double* d_c,
+                                         const int32_t* d_mask, int batch, double* d_P, lmpc_contact_out* d_out,
+                                         void* stream) {
+    if (batch < 0 || (batch > 0 && (!cfg || !d_K || !d_c || !d_mask || !d_P || !good_solver_cfg(*cfg))))
+        return LMPC_ERR_ARG;
+    if (batch == 0) return LMPC_OK;
+    hipLaunchKernelGGL(lmpc_contact_solve_kernel, dim3((batch + BLOCK_ROBOTS - 1) / BLOCK_ROBOTS), dim3(BLOCK), 0,
+                       (hipStream_t)stream, d_K, d_c, d_mask, batch, caps_of(*cfg), d_P, d_out);
+    return hipGetLastError() == hipSuccess ? LMPC_OK : LMPC_ERR_LAUNCH;
+}
+
+extern "C" int lmpc_contact_step_device(const lmpc_rbd_model* model, const lmpc_contact_cfg* cfg,
+                                        const lmpc_rbd_state* d_state, const double* d_tau, int64_t tau_stride,
+                                        const int32_t* d_mask, int64_t mask_stride, int batch, int substeps,
+                                        lmpc_rbd_state* d_next, lmpc_sim_out* d_out, lmpc_contact_out* d_cout,
+                                        void* d_work, size_t work_bytes, void* stream) {
+    if (batch < 0 || (batch > 0 && (!model || !cfg || !d_state || !d_tau || !d_mask || !d_next || tau_stride < 12 ||
+                                    mask_stride < 4 || substeps < 1 || !good_step_cfg(*cfg) ||
+                                    (d_work && work_bytes < lmpc_contact_work_bytes(batch)))))
+        return LMPC_ERR_ARG;
+    if (batch == 0) return LMPC_OK;
+    const StepArgs a{cfg->dt, cfg->ground_z, cfg->recover_speed, cfg->force_threshold, (int)cfg->use_gap,
+                     (int)cfg->touch_rule, caps_of(*cfg)};
+    const dim3 grid((batch + BLOCK_ROBOTS - 1) / BLOCK_ROBOTS), block(BLOCK);
+    const hipStream_t s = (hipStream_t)stream;
+    if (!d_work) {
+        hipLaunchKernelGGL((lmpc_contact_step_kernel<FUSED>), grid, block, 0, s, *model, d_state, d_tau,
+                           (long long)tau_stride, d_mask, (long long)mask_stride, batch, substeps, a, d_next, d_out, d_cout,
+                           Work{}, 1);
+        return hipGetLastError() == hipSuccess ? LMPC_OK : LMPC_ERR_LAUNCH;
+    }
+    // the three-launch form, per substep: K and c into the workspace, the bare solve on them, the back-substitution.
+    // The same arithmetic in the same order as the fused kernel: the same bits.
+    const Work wk = work_of(d_work, batch);
+    const lmpc_rbd_state* from = d_state;
+    for (int step = 0; step < substeps; ++step) {
+        const bool last = step == substeps - 1;
+        hipLaunchKernelGGL((lmpc_contact_step_kernel<TERMS>), grid, block, 0, s, *model, from, d_tau,
+                           (long long)tau_stride, d_mask, (long long)mask_stride, batch, 1, a, (lmpc_rbd_state*)nullptr,
+                           (lmpc_sim_out*)nullptr, (lmpc_contact_out*)nullptr, wk, 1);
+        hipLaunchKernelGGL(lmpc_contact_solve_kernel, grid, block, 0, s, wk.K, wk.c, wk.mask, batch, a.caps, wk.P, wk.out);
+        hipLaunchKernelGGL((lmpc_contact_step_kernel<APPLY>), grid, block, 0, s, *model, from, d_tau,
+                           (long long)tau_stride, d_mask, (long long)mask_stride, batch, 1, a, d_next,
+                           last ? d_out : (lmpc_sim_out*)nullptr, last ? d_cout : (lmpc_contact_out*)nullptr, wk,
+                           step == 0 ? 1 : 0);
+        from = d_next;
+    }
+    return hipGetLastError() == hipSuccess ? LMPC_OK : LMPC_ERR_LAUNCH;
+}

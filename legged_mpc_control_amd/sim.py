@@ -11,7 +11,9 @@ integrator on top of it, and a device loop that closes the whole-body controller
 
 The contact rule is fixed and deterministic, not a complementarity solution: feet whose normal force comes out
 negative are released and never re-added within a step, the friction cone is not enforced, and held feet drift by
-O(dt^2) per step (include/lmpc/lmpc_sim.h).  The device functions are HIP kernels; there is no CPU fallback.
+O(dt^2) per step (include/lmpc/lmpc_sim.h).  The plant step that does solve a friction-cone complementarity problem is
+`contact.step` / `contact.step_device` (include/lmpc/lmpc_contact.h); `WbcSim(..., contact=contact.cfg())` runs on it.
+The device functions are HIP kernels; there is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -150,11 +152,14 @@ class WbcSim:
     (state -> torques), then `lmpc_sim_step_device` with tau read by stride from the pipeline's x and the candidate
     contacts by stride from the targets -- on one stream, with no host synchronisation in between."""
 
-    def __init__(self, model: N.LmpcRbdModel, max_batch: int, c: N.LmpcSimCfg = None, device: int = 0):
+    def __init__(self, model: N.LmpcRbdModel, max_batch: int, c: N.LmpcSimCfg = None, device: int = 0, contact=None):
+        """contact: an `lmpc_contact_cfg` (contact.cfg(...)) steps the plant with the frictional contact model
+        (`lmpc_contact_step_device`, the targets' contacts as its mask) and `c` is not used; None: the present plant."""
         import torch
 
         self.model = model
         self.cfg = c if c is not None else cfg()
+        self.contact = contact
         self.max_batch = int(max_batch)
         self.device = device
         self.pipeline = WbcPipeline(model, max_batch, device)
@@ -190,8 +195,14 @@ class WbcSim:
         with torch.cuda.stream(s):
             for t in range(ticks):
                 d_x, d_status = self.pipeline.solve_device(d_state, d_target, s)
-                step_device(self.model, self.cfg, d_state, d_x[:, TAU_OFFSET:TAU_OFFSET + 12], d_contact, d_state, d_out,
-                            substeps, s)
+                if self.contact is None:
+                    step_device(self.model, self.cfg, d_state, d_x[:, TAU_OFFSET:TAU_OFFSET + 12], d_contact, d_state,
+                                d_out, substeps, s)
+                else:
+                    from . import contact as C
+
+                    C.step_device(self.model, self.contact, d_state, d_x[:, TAU_OFFSET:TAU_OFFSET + 12], d_contact,
+                                  d_state, d_out, None, substeps, s)
                 if log:
                     logs["states"][t].copy_(d_state)
                     logs["held"][t].copy_(flags[:, 0:4])

@@ -11,7 +11,9 @@
     see the plant's state: after every plant step the loop reads sensors off the plant (`est.sensors_from_plant_device`)
     and runs the reference's Kalman filter (`est.update_device`); the advance and the WBC then read the estimated
     state and a shadow `lmpc_sim_out` with the estimate's feet and contact flags, while the plant and the candidate
-    rule keep reading the true ones.
+    rule keep reading the true ones.  With `plant=contact.cfg()` the plant step is `lmpc_contact_step_device` (the
+    frictional contact model, include/lmpc/lmpc_contact.h): every foot is in its mask on every step and the candidate
+    launch is gone.
 
 What is restated from the reference and what is this library's choice (zero latency, the candidate rule, `touch` as
 the contact flag, the standing mode's foot targets, what a failed stage leaves): include/lmpc/lmpc_stack.h.  The
@@ -24,6 +26,7 @@ import ctypes
 import numpy as np
 
 from . import _native as N
+from . import contact as C
 from . import est as E
 from . import sim as S
 from .hoqp import check_device_tensor
@@ -201,10 +204,17 @@ class StackLoop:
 
     def __init__(self, model: N.LmpcRbdModel, params: N.LmpcParams, horizon: int, max_batch: int,
                  rollout_cfg: N.LmpcRolloutCfg, sim_cfg: N.LmpcSimCfg, wbc_per_mpc: int, substeps: int = 1,
-                 template: N.LmpcWbcTarget = None, device: int = 0, estimator: N.LmpcEstCfg = None):
+                 template: N.LmpcWbcTarget = None, device: int = 0, estimator: N.LmpcEstCfg = None,
+                 plant: N.LmpcContactCfg = None, plant_split: bool = False):
         """estimator: an `lmpc_est_cfg` (est.cfg(dt=...)) closes the loop on the Kalman filter's estimate instead of the
         plant's own state; its dt must be the low-level tick's, substeps * sim_cfg.dt.  None: the plant's state is the
-        feedback, exactly as without this option."""
+        feedback, exactly as without this option.
+
+        plant: an `lmpc_contact_cfg` (contact.cfg(dt=...)) steps the plant with the frictional contact model
+        (`lmpc_contact_step_device`) instead of `lmpc_sim_step_device`: every foot is in the mask on every step, so the
+        candidate rule and its launch are gone; its dt and ground_z must be sim_cfg's.  None: the present plant,
+        exactly as without this option.  plant_split: run that step in its three-launch form on a workspace the loop
+        owns (the same bits; DESIGN.md 4h has the timings of both)."""
         import torch
 
         if max_batch < 1:
@@ -212,8 +222,12 @@ class StackLoop:
         if wbc_per_mpc < 1 or substeps < 1:
             raise ValueError("wbc_per_mpc and substeps must be positive")
         check_rates(params, sim_cfg, wbc_per_mpc, substeps)
-        if not sim_cfg.unilateral:
+        if plant is None and not sim_cfg.unilateral:
             raise ValueError("the loop's candidate rule needs the plant's unilateral rule (sim_cfg.unilateral = 1)")
+        if plant is not None and not (abs(plant.dt - sim_cfg.dt) <= 1e-12 and plant.ground_z == sim_cfg.ground_z):
+            raise ValueError(f"plant dt {plant.dt} / ground_z {plant.ground_z} are not sim_cfg's {sim_cfg.dt} / "
+                             f"{sim_cfg.ground_z}")
+        self.plant = plant
         self.model, self.params, self.H = model, params, int(horizon)
         self.max_batch, self.device = int(max_batch), device
         self.rollout_cfg, self.sim_cfg = rollout_cfg, sim_cfg
@@ -228,6 +242,12 @@ class StackLoop:
         self.d_qp_iters = torch.zeros(self.max_batch, dtype=torch.int32, device=dev)
         self.d_target = torch.zeros((self.max_batch, TARGET_BYTES), dtype=torch.uint8, device=dev)
         self.d_candidates = torch.zeros((self.max_batch, 4), dtype=torch.int32, device=dev)
+        if plant is not None:
+            self.d_candidates.fill_(1)  # the mask: every foot, on every step
+            self.d_contact_out = torch.zeros((self.max_batch, C.OUT_BYTES), dtype=torch.uint8, device=dev)
+        self.d_plant_work = None
+        if plant is not None and plant_split:
+            self.d_plant_work = torch.zeros(C.work_bytes(self.max_batch), dtype=torch.uint8, device=dev)
         self.estimator = estimator
         if estimator is not None:
             if not abs(estimator.dt - self.substeps * sim_cfg.dt) <= 1e-12:
@@ -293,7 +313,8 @@ class StackLoop:
         T, W = int(mpc_ticks), self.wbc_per_mpc
         d_grf, d_qst, d_qit = self.d_grf[:B], self.d_qp_status[:B], self.d_qp_iters[:B]
         d_target, d_cand = self.d_target[:B], self.d_candidates[:B]
-        est = self.estimator
+        est, plant = self.estimator, self.plant
+        d_cout = self.d_contact_out[:B] if plant is not None else None
         d_fb_state, d_fb_out = d_state, d_sim_out  # what the advance and the WBC read
         if est is not None:
             d_sens, d_filt, d_eout = self.d_sensors[:B], self.d_filter[:B], self.d_est_out[:B]
@@ -312,6 +333,8 @@ class StackLoop:
                         tau=torch.empty((K, B, 12), dtype=torch.float64, device=dev),
                         candidates=torch.empty((K, B, 4), dtype=torch.int32, device=dev),
                         wbc_status=torch.empty((K, B), dtype=torch.int32, device=dev))
+            if plant is not None:
+                logs["contact_out"] = torch.empty((K, B, C.OUT_BYTES), dtype=torch.uint8, device=dev)
             if est is not None:
                 for name, width in (("sensors", E.SENSORS_BYTES), ("state_est", STATE_BYTES), ("filter", E.FILTER_BYTES),
                                     ("est_out", E.OUT_BYTES), ("shadow", S.OUT_BYTES)):
@@ -334,10 +357,15 @@ class StackLoop:
                     logs["qp_iters"][t].copy_(d_qit)
                     logs["target"][t].copy_(d_target)
                 for i in range(W):
-                    candidates_device(d_sim_out, d_cand, s)
+                    if plant is None:
+                        candidates_device(d_sim_out, d_cand, s)
                     d_x, d_wst = self.pipeline.solve_device(d_fb_state, d_target, s)
                     d_tau = d_x[:, S.TAU_OFFSET:S.TAU_OFFSET + 12]
-                    S.step_device(self.model, self.sim_cfg, d_state, d_tau, d_cand, d_state, d_sim_out, self.substeps, s)
+                    if plant is None:
+                        S.step_device(self.model, self.sim_cfg, d_state, d_tau, d_cand, d_state, d_sim_out, self.substeps, s)
+                    else:
+                        C.step_device(self.model, plant, d_state, d_tau, d_cand, d_state, d_sim_out, d_cout, self.substeps,
+                                      s, self.d_plant_work)
                     if est is not None:
                         self._est_tick += 1
                         E.sensors_from_plant_device(self.model, est, d_state, d_sim_out, d_sens, self._est_tick, 0, d_gait, s)
@@ -349,6 +377,8 @@ class StackLoop:
                         logs["tau"][k].copy_(d_tau)
                         logs["candidates"][k].copy_(d_cand)
                         logs["wbc_status"][k].copy_(d_wst)
+                        if plant is not None:
+                            logs["contact_out"][k].copy_(d_cout)
                         if est is not None:
                             logs["sensors"][k].copy_(d_sens)
                             logs["state_est"][k].copy_(d_fb_state)
@@ -359,6 +389,8 @@ class StackLoop:
             flags = logs["out"].view(torch.int32)[..., S.OUT_BYTES // 4 - 10:]  # held (4), touch (4), status, reserved
             logs["cmd"] = logs["robots"][..., :N.COMMAND_BYTES]
             logs["held"], logs["touch"], logs["sim_status"] = flags[..., 0:4], flags[..., 4:8], flags[..., 8]
+            if plant is not None:
+                logs["mode"] = logs["contact_out"].view(torch.int32)[..., C.MODE_OFFSET // 4:C.MODE_OFFSET // 4 + 4]
             if est is not None:
                 logs["est_status"] = logs["est_out"].view(torch.int32)[..., E.OUT_BYTES // 4 - 2]
         return logs

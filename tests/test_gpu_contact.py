@@ -1,0 +1,354 @@
+"""GPU tests of the frictional contact model's kernels (lmpc_contact.hip through include/lmpc/lmpc_contact.h): the
+device step and the device bare solve against the host functions (the same arithmetic compiled for the CPU), substeps,
+aliasing, batch independence, bounds, strided inputs and argument checks.
+
+Pool.  Per robot (Go1, A1) 67 states in the style of test_sim_host.make_sim_states, each lifted so that one of its feet
+lies on the ground z = 0, 0.1 mm above or below it, or 2 mm below it (the others above and below), with masks that are
+all ones on two robots of three and a pattern otherwise.  Two configurations: "gap" (mu 0.6, the bias on, touch by the
+force threshold) and "flat" (mu 0.3, use_gap = 0, geometric touch).  The pool is checked on the CPU against
+tests/contact_ref.py: no case on a tie (strict-complementarity margin >= 1e-6), and the fixture fails if one is.
+
+Device vs host.  The two sides differ only through sin / cos (no contraction on either side), amplified by
+cond K <= 65 and, in qdd, by 1 / dt.  Modes, held, touch, status, sweeps and polish rounds match bit for bit; every
+double lies within 1e-10 relative to max(1, |host|) (the issue's bar; lmpc_sim's worst device-vs-host figure is 7.6e-13).
+Geometric touch flags are compared on the feet that end more than 1e-9 m from the ground (tests/test_contact_host.py).
+Every run prints what it measures; on an MI355X the worst figures are force 1.3e-12, qdd 6.2e-13, next state 5.4e-14,
+w 2.8e-14, foot_vel 2.0e-14 (three substeps: qdd 4.3e-13).  The bare solve has no sin / cos in it and agrees bit for
+bit.
+"""
+import ctypes
+
+import numpy as np
+import pytest
+
+import contact_ref as C
+import rbd_ref as R
+from test_rbd_host import model_json, preset
+from test_sim_host import DT, PATTERNS, make_sim_states
+
+pytestmark = pytest.mark.gpu
+
+BAR = 1e-10
+BATCHES = (1, 5, 16, 17, 67)
+GUARD = 8
+FIELDS = ("qdd", "force", "foot_pos", "foot_vel")
+CFGS = {"gap": dict(mu=0.6, use_gap=1, touch_rule=1, force_threshold=5.0),
+        "flat": dict(mu=0.3, use_gap=0, touch_rule=0)}
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    import torch
+
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    torch.cuda.init()
+    from legged_mpc_control_amd import contact, rbd, sim
+
+    return torch, rbd, sim, contact
+
+
+def dev(a, ref):
+    return float(np.max(np.abs(np.asarray(a) - np.asarray(ref)) / np.maximum(1.0, np.abs(np.asarray(ref)))))
+
+
+def vec(st):
+    return np.frombuffer(bytes(st), dtype=np.float64)
+
+
+@pytest.fixture(scope="module")
+def pool():
+    """Per robot: 67 states, torques and masks; per configuration the host's step (and three-substep step) and the
+    reference's K and c for the bare solve; the tie check against contact_ref."""
+    from legged_mpc_control_amd import contact, rbd
+
+    out = {}
+    for r, name in enumerate(("go1", "a1")):
+        md, m = model_json(name), preset(name)
+        states, taus = make_sim_states(md, 950 + r, 67)
+        masks = []
+        for i, s in enumerate(states):
+            zs = np.sort(R.terms(md, s)["foot_pos"][2::3])
+            s[5] -= zs[i % 4] + [0.0, 1e-4, -1e-4, -2e-3][(i // 4) % 4]
+            masks.append((1, 1, 1, 1) if i % 3 else PATTERNS[(5 * i + 7) % 16])
+        st = [rbd.state_from_vector(s) for s in states]
+        p = dict(model=m, states=st, taus=np.array(taus), masks=np.array(masks, dtype=np.int32), cfg={}, step={},
+                 step3={}, K={}, c={}, ref={})
+        for key, kw in CFGS.items():
+            cf = contact.cfg(dt=DT, ground_z=0.0, **kw)
+            refs = []
+            for s, tau, mask in zip(states, taus, masks):
+                ref = C.step(md, s, tau, mask, DT, 0.0, kw["mu"], bool(kw["use_gap"]), 0.0, kw["touch_rule"],
+                             kw.get("force_threshold", 50.0))
+                assert ref["margin"] >= 1e-6, "a case on a tie: choose another seed"
+                if kw["touch_rule"] == 1:
+                    mag = np.linalg.norm(ref["force"].reshape(4, 3), axis=1)
+                    assert np.min(np.abs(mag - kw["force_threshold"])) > 1e-6 * kw["force_threshold"]
+                refs.append(ref)
+            p["cfg"][key], p["ref"][key] = cf, refs
+            p["K"][key], p["c"][key] = np.array([x["K"].reshape(144) for x in refs]), np.array([x["c"] for x in refs])
+            p["step"][key] = [contact.step(m, cf, s, tau, mask) for s, tau, mask in zip(st, taus, masks)]
+            if name == "go1" and key == "gap":  # test_substeps_on_the_device's 17 robots
+                p["step3"][key] = [contact.step(m, cf, s, tau, mask, substeps=3)
+                                   for s, tau, mask in zip(st[:17], taus[:17], masks[:17])]
+        modes = sorted(set(int(x) for key in CFGS for ref in p["ref"][key] for x in ref["modes"]))
+        assert modes == list(range(11)), f"{name}: the pool shows modes {modes}"
+        out[name] = p
+    return out
+
+
+def upload(gpu, p, idx):
+    torch, rbd, sim, contact = gpu
+    d_state = torch.from_numpy(rbd.pack([p["states"][i] for i in idx])).cuda()
+    d_tau = torch.from_numpy(np.ascontiguousarray(p["taus"][idx])).cuda()
+    d_mask = torch.from_numpy(np.ascontiguousarray(p["masks"][idx])).cuda()
+    return d_state, d_tau, d_mask
+
+
+def run_step(gpu, p, key, idx, guard=0, substeps=1, in_place=False, with_out=True, with_cout=True):
+    """lmpc_contact_step_device -> (next uint8 [B + guard][288], out [B + guard][472] or None, cout [B + guard][176] or
+    None); guard rows prefilled with 0xA5."""
+    torch, rbd, sim, contact = gpu
+    B = len(idx)
+    d_state, d_tau, d_mask = upload(gpu, p, idx)
+    d_out = torch.full((B + guard, sim.OUT_BYTES), 0xA5, dtype=torch.uint8, device="cuda") if with_out else None
+    d_cout = torch.full((B + guard, contact.OUT_BYTES), 0xA5, dtype=torch.uint8, device="cuda") if with_cout else None
+    d_next = torch.full((B + guard, rbd.STATE_BYTES), 0xA5, dtype=torch.uint8, device="cuda")
+    if in_place:
+        d_next[:B] = d_state
+        d_state = d_next[:B]
+    contact.step_device(p["model"], p["cfg"][key], d_state, d_tau, d_mask, d_next[:B], d_out[:B] if with_out else None,
+                        d_cout[:B] if with_cout else None, substeps)
+    torch.cuda.synchronize()
+    return d_next.cpu().numpy(), (d_out.cpu().numpy() if with_out else None), (d_cout.cpu().numpy() if with_cout else None)
+
+
+def outs_of(gpu, raw_out, raw_cout):
+    from legged_mpc_control_amd import _native as N
+
+    torch, rbd, sim, contact = gpu
+    return (sim.out_dict(N.LmpcSimOut.from_buffer_copy(raw_out.tobytes())),
+            contact.out_dict(N.LmpcContactOut.from_buffer_copy(raw_cout.tobytes())))
+
+
+def compare(gpu, p, key, b, nxt_row, out_row, cout_row, host, worst):
+    """One robot, device against host: flags and modes bit for bit, doubles into `worst`."""
+    torch, rbd, sim, contact = gpu
+    hn, ho, hc = host
+    d, dc = outs_of(gpu, out_row, cout_row)
+    h, hc = sim.out_dict(ho), contact.out_dict(hc)
+    assert d["status"] == h["status"] == 0 and dc["status"] == hc["status"] == 0
+    assert np.array_equal(dc["mode"], hc["mode"]) and np.array_equal(d["held"], h["held"])
+    assert (dc["sweeps"], dc["polish"]) == (hc["sweeps"], hc["polish"])
+    if p["cfg"][key].touch_rule == 1:
+        assert np.array_equal(d["touch"], h["touch"])
+    else:
+        clear = np.abs(h["foot_pos"][2::3]) > 1e-9
+        assert np.array_equal(d["touch"][clear], h["touch"][clear])
+    for l in range(4):
+        if hc["mode"][l] >= contact.MODE_APEX:
+            assert np.array_equal(d["force"][3 * l:3 * l + 3], np.zeros(3))
+            assert not np.any(np.signbit(d["force"][3 * l:3 * l + 3]))
+    for k in FIELDS:
+        worst[k] = max(worst.get(k, 0.0), dev(d[k], h[k]))
+    worst["next"] = max(worst.get("next", 0.0), dev(nxt_row.view(np.float64), vec(hn)))
+    worst["w"] = max(worst.get("w", 0.0), dev(dc["w"], hc["w"]))
+    worst["gap"] = max(worst.get("gap", 0.0), dev(dc["gap"], hc["gap"]))
+    worst["res"] = max(worst.get("res", 0.0), dc["res_primal"], dc["res_dual"])
+
+
+@pytest.mark.parametrize("name,batch,key", [("go1", b, "gap") for b in BATCHES] + [("a1", 17, "gap"), ("go1", 17, "flat"),
+                                                                                  ("a1", 67, "flat")])
+def test_step_device_matches_host(gpu, pool, name, batch, key):
+    p = pool[name]
+    nxt, out, cout = run_step(gpu, p, key, list(range(batch)))
+    worst = {}
+    for b in range(batch):
+        compare(gpu, p, key, b, nxt[b], out[b], cout[b], p["step"][key][b], worst)
+    print(f"{name} batch {batch} {key}: step, device vs host", {k: f"{v:.1e}" for k, v in worst.items()})
+    assert worst.pop("res") <= 1e-9
+    for k, v in worst.items():
+        assert v <= BAR, f"{k}: {v:.2e} > {BAR:.0e}"
+
+
+@pytest.mark.parametrize("name,batch,key", [("go1", 5, "gap"), ("go1", 67, "gap"), ("a1", 17, "flat")])
+def test_solve_device_matches_host(gpu, pool, name, batch, key):
+    """The bare problem (the reference's K and c): the device's P, w and modes against the host's."""
+    torch, rbd, sim, contact = gpu
+    from legged_mpc_control_amd import _native as N
+
+    p = pool[name]
+    cf = p["cfg"][key]
+    d_K = torch.from_numpy(np.ascontiguousarray(p["K"][key][:batch])).cuda()
+    d_c = torch.from_numpy(np.ascontiguousarray(p["c"][key][:batch])).cuda()
+    d_mask = torch.from_numpy(np.ascontiguousarray(p["masks"][:batch])).cuda()
+    d_P = torch.full((batch + GUARD, 12), float("nan"), dtype=torch.float64, device="cuda")
+    d_out = torch.full((batch + GUARD, contact.OUT_BYTES), 0xA5, dtype=torch.uint8, device="cuda")
+    contact.solve_device(cf, d_K, d_c, d_mask, d_P[:batch], d_out[:batch])
+    d_P2 = torch.zeros((batch, 12), dtype=torch.float64, device="cuda")
+    contact.solve_device(cf, d_K, d_c, d_mask, d_P2, None)
+    torch.cuda.synchronize()
+    P, raw = d_P.cpu().numpy(), d_out.cpu().numpy()
+    assert np.all(np.isnan(P[batch:])) and np.all(raw[batch:] == 0xA5)
+    assert np.array_equal(P[:batch], d_P2.cpu().numpy())
+    worst = {"P": 0.0, "w": 0.0, "ref_P": 0.0}
+    for b in range(batch):
+        hP, ho = contact.solve(cf, p["K"][key][b], p["c"][key][b], p["masks"][b])
+        h = contact.out_dict(ho)
+        d = contact.out_dict(N.LmpcContactOut.from_buffer_copy(raw[b].tobytes()))
+        assert d["status"] == h["status"] == 0 and np.array_equal(d["mode"], h["mode"])
+        assert np.array_equal(d["mode"], p["ref"][key][b]["modes"])
+        assert (d["sweeps"], d["polish"]) == (h["sweeps"], h["polish"]) and np.array_equal(d["gap"], np.zeros(4))
+        # the same inputs and the same arithmetic, no sin / cos: the bare solve agrees bit for bit
+        assert np.array_equal(P[b], hP) and np.array_equal(d["w"], h["w"])
+        assert (d["res_primal"], d["res_dual"]) == (h["res_primal"], h["res_dual"])
+        worst["ref_P"] = max(worst["ref_P"], dev(P[b], p["ref"][key][b]["P"]))
+    print(f"{name} batch {batch} {key}: bare solve, device vs host bit for bit; vs contact_ref {worst['ref_P']:.1e}")
+    assert worst["ref_P"] <= 1e-7
+
+
+def test_substeps_on_the_device(gpu, pool):
+    """substeps = 3 equals three device calls of one bit for bit, and agrees with the host's three chained steps."""
+    torch, rbd, sim, contact = gpu
+    p = pool["go1"]
+    idx = list(range(17))
+    n3, o3, c3 = run_step(gpu, p, "gap", idx, substeps=3)
+    d_state, d_tau, d_mask = upload(gpu, p, idx)
+    d_out = torch.zeros((17, sim.OUT_BYTES), dtype=torch.uint8, device="cuda")
+    d_cout = torch.zeros((17, contact.OUT_BYTES), dtype=torch.uint8, device="cuda")
+    for _ in range(3):
+        d_next = torch.zeros_like(d_state)
+        contact.step_device(p["model"], p["cfg"]["gap"], d_state, d_tau, d_mask, d_next, d_out, d_cout)
+        d_state = d_next
+    torch.cuda.synchronize()
+    assert np.array_equal(n3, d_state.cpu().numpy()) and np.array_equal(o3, d_out.cpu().numpy())
+    assert np.array_equal(c3, d_cout.cpu().numpy())
+    worst = {}
+    for b in idx:
+        compare(gpu, p, "gap", b, n3[b], o3[b], c3[b], p["step3"]["gap"][b], worst)
+    print("three substeps, device vs host", {k: f"{v:.1e}" for k, v in worst.items()})
+    worst.pop("res")
+    for k, v in worst.items():
+        assert v <= BAR, f"{k}: {v:.2e} > {BAR:.0e}"
+
+
+@pytest.mark.parametrize("name,batch,key,substeps", [("go1", 67, "gap", 1), ("go1", 17, "gap", 3), ("a1", 5, "flat", 2)])
+def test_three_launch_form_equals_fused(gpu, pool, name, batch, key, substeps):
+    """With a workspace the step runs as terms + bare solve + back-substitution: the same bits as the fused kernel, in
+    place too, nothing written past the batch, and a workspace that is too small is refused."""
+    torch, rbd, sim, contact = gpu
+    p = pool[name]
+    idx = list(range(batch))
+    nxt, out, cout = run_step(gpu, p, key, idx, guard=GUARD, substeps=substeps)
+    d_state, d_tau, d_mask = upload(gpu, p, idx)
+    need = contact.work_bytes(batch)
+    assert need == batch * 1544
+    d_work = torch.full((need + 64,), 0xA5, dtype=torch.uint8, device="cuda")
+    d_next = torch.full((batch + GUARD, rbd.STATE_BYTES), 0xA5, dtype=torch.uint8, device="cuda")
+    d_out = torch.full((batch + GUARD, sim.OUT_BYTES), 0xA5, dtype=torch.uint8, device="cuda")
+    d_cout = torch.full((batch + GUARD, contact.OUT_BYTES), 0xA5, dtype=torch.uint8, device="cuda")
+    contact.step_device(p["model"], p["cfg"][key], d_state, d_tau, d_mask, d_next[:batch], d_out[:batch], d_cout[:batch],
+                        substeps, None, d_work[:need])
+    torch.cuda.synchronize()
+    assert np.array_equal(d_next.cpu().numpy(), nxt) and np.array_equal(d_out.cpu().numpy(), out)
+    assert np.array_equal(d_cout.cpu().numpy(), cout)
+    assert np.all(d_work[need:].cpu().numpy() == 0xA5)
+    contact.step_device(p["model"], p["cfg"][key], d_state, d_tau, d_mask, d_state, None, None, substeps, None,
+                        d_work[:need])
+    torch.cuda.synchronize()
+    assert np.array_equal(d_state.cpu().numpy(), nxt[:batch])
+    with pytest.raises(ValueError):
+        contact.step_device(p["model"], p["cfg"][key], d_state, d_tau, d_mask, d_state, None, None, substeps, None,
+                            d_work[:need - 1])
+
+
+def test_in_place_and_without_outs(gpu, pool):
+    p = pool["go1"]
+    idx = list(range(17))
+    apart, out, cout = run_step(gpu, p, "gap", idx, substeps=2)
+    same, out_same, cout_same = run_step(gpu, p, "gap", idx, substeps=2, in_place=True)
+    assert np.array_equal(apart, same) and np.array_equal(out, out_same) and np.array_equal(cout, cout_same)
+    bare, none, none2 = run_step(gpu, p, "gap", idx, substeps=2, with_out=False, with_cout=False)
+    assert none is None and none2 is None and np.array_equal(bare, apart)
+    only, out_only, none3 = run_step(gpu, p, "gap", idx, substeps=2, with_cout=False)
+    assert none3 is None and np.array_equal(only, apart) and np.array_equal(out_only, out)
+    assert not np.array_equal(apart, gpu[1].pack([p["states"][i] for i in idx]))
+
+
+def test_batch_independence_and_guards(gpu, pool):
+    """A robot's bytes do not depend on its position in the batch nor on its neighbours (whose solves take other
+    numbers of sweeps); nothing is written past the batch."""
+    p = pool["go1"]
+    for key, probe in (("gap", 7), ("flat", 10)):
+        n_alone, o_alone, c_alone = run_step(gpu, p, key, [probe], substeps=2)
+        others = [i for i in range(67) if i != probe]
+        for pos in (0, 66, 33):
+            idx = others[:pos] + [probe] + others[pos:]
+            assert len(idx) == 67
+            nxt, out, cout = run_step(gpu, p, key, idx, guard=GUARD, substeps=2)
+            assert np.array_equal(nxt[pos], n_alone[0]) and np.array_equal(out[pos], o_alone[0]), f"position {pos}"
+            assert np.array_equal(cout[pos], c_alone[0]), f"position {pos}"
+            assert np.all(nxt[67:] == 0xA5) and np.all(out[67:] == 0xA5) and np.all(cout[67:] == 0xA5)
+    nxt, out, cout = run_step(gpu, p, "gap", list(range(17)), guard=GUARD, in_place=True)
+    assert np.all(nxt[17:] == 0xA5) and np.all(out[17:] == 0xA5) and np.all(cout[17:] == 0xA5)
+    assert not np.all(out[16] == 0xA5) and not np.all(cout[16] == 0xA5)
+    sweeps = set(int(c.sweeps) for _, _, c in p["step"]["gap"])
+    assert len(sweeps) > 1, "every robot takes the same number of sweeps: the frozen-quad path is not exercised"
+
+
+def test_strided_inputs(gpu, pool):
+    """tau read from a [B][3][42] tensor (offset 30 of the last level) and the mask from packed targets equal the
+    contiguous inputs bit for bit."""
+    torch, rbd, sim, contact = gpu
+    p = pool["go1"]
+    idx = list(range(17))
+    nxt, out, cout = run_step(gpu, p, "gap", idx)
+    d_state, d_tau, d_mask = upload(gpu, p, idx)
+    d_x = torch.full((17, 3, 42), float("nan"), dtype=torch.float64, device="cuda")
+    d_x[:, -1, sim.TAU_OFFSET:] = d_tau
+    targets = [rbd.target(forces_des=np.full(12, np.nan), contact=p["masks"][i]) for i in idx]
+    d_target = torch.from_numpy(rbd.pack(targets)).cuda()
+    tau_view, mask_view = d_x[:, -1, sim.TAU_OFFSET:sim.TAU_OFFSET + 12], sim.target_contacts(d_target)
+    assert tau_view.stride() == (126, 1) and mask_view.stride() == (88, 1)
+    d_next = torch.zeros_like(d_state)
+    d_out = torch.zeros((17, sim.OUT_BYTES), dtype=torch.uint8, device="cuda")
+    d_cout = torch.zeros((17, contact.OUT_BYTES), dtype=torch.uint8, device="cuda")
+    contact.step_device(p["model"], p["cfg"]["gap"], d_state, tau_view, mask_view, d_next, d_out, d_cout)
+    torch.cuda.synchronize()
+    assert np.array_equal(d_next.cpu().numpy(), nxt) and np.array_equal(d_out.cpu().numpy(), out)
+    assert np.array_equal(d_cout.cpu().numpy(), cout)
+
+
+def test_device_argument_checks(gpu, pool):
+    torch, rbd, sim, contact = gpu
+    p = pool["go1"]
+    cf = p["cfg"]["gap"]
+    d_state, d_tau, d_mask = upload(gpu, p, list(range(4)))
+    d_next = torch.zeros_like(d_state)
+    d_out = torch.zeros((4, sim.OUT_BYTES), dtype=torch.uint8, device="cuda")
+    d_cout = torch.zeros((4, contact.OUT_BYTES), dtype=torch.uint8, device="cuda")
+    with pytest.raises(ValueError):
+        contact.step_device(p["model"], cf, d_state, d_tau[:3], d_mask, d_next, d_out, d_cout)
+    with pytest.raises(ValueError):
+        contact.step_device(p["model"], cf, d_state, d_tau, d_mask.cpu(), d_next, d_out, d_cout)
+    with pytest.raises(ValueError):
+        contact.step_device(p["model"], cf, d_state, d_tau.t().contiguous().t(), d_mask, d_next, d_out, d_cout)
+    with pytest.raises(ValueError):
+        contact.step_device(p["model"], cf, d_state, d_tau, d_mask, d_out, d_out, d_cout)
+    with pytest.raises(ValueError):
+        contact.step_device(p["model"], cf, d_state, d_tau, d_mask, d_next, d_out, d_out)
+    with pytest.raises(RuntimeError):
+        contact.step_device(p["model"], cf, d_state, d_tau, d_mask, d_next, d_out, d_cout, substeps=0)
+    with pytest.raises(RuntimeError):
+        contact.step_device(p["model"], contact.cfg(mu=0.0), d_state, d_tau, d_mask, d_next, d_out, d_cout)
+    d_K = torch.zeros((4, 144), dtype=torch.float64, device="cuda")
+    d_c = torch.zeros((4, 12), dtype=torch.float64, device="cuda")
+    d_P = torch.zeros((4, 12), dtype=torch.float64, device="cuda")
+    with pytest.raises(ValueError):
+        contact.solve_device(cf, d_K[:, :143], d_c, d_mask, d_P)
+    with pytest.raises(ValueError):
+        contact.solve_device(cf, d_K, d_c[:3], d_mask, d_P)
+    with pytest.raises(ValueError):
+        contact.solve_device(cf, d_K, d_c, d_mask, d_P.cpu())
+    with pytest.raises(ValueError):
+        contact.solve_device(cf, d_K, d_c, d_mask, d_P, d_out)
+    assert ctypes.sizeof(type(cf)) == contact.CFG_BYTES

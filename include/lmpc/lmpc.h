@@ -94,7 +94,7 @@ typedef struct lmpc_params {
     double q_weights[12];
     double r_weights[12];
     double robot_mass;
-    double trunk_inertia[9]; /* row-major, body frame */
+    double trunk_inertia[9]; /* row-major, body frame; finite with a positive determinant, else LMPC_ERR_ARG */
     double mu;               /* friction coefficient, reference 0.3 */
     double f_max;            /* normal-force bound, reference 180 N */
     double gravity;          /* reference 9.8 */

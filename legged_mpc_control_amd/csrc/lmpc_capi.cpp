@@ -117,9 +117,20 @@ void fill_options(lmpc::DevParams& d, const lmpc_options* o) {
 bool params_ok(const lmpc_params* p) {
     if (!p) return false;
     if (!(p->robot_mass > 0.0) || !(p->dt > 0.0) || !(p->mu > 0.0) || !(p->f_max >= 0.0)) return false;
-    for (int i = 0; i < 12; ++i)
+    if (!std::isfinite(p->robot_mass) || !std::isfinite(p->dt) || !std::isfinite(p->mu) || !std::isfinite(p->f_max) ||
+        !std::isfinite(p->gravity))
+        return false;
+    for (int i = 0; i < 12; ++i) {
         if (!(p->r_weights[i] > 0.0) || !(p->q_weights[i] >= 0.0)) return false;  // R > 0: strictly convex
-    return true;
+        if (!std::isfinite(p->r_weights[i]) || !std::isfinite(p->q_weights[i])) return false;
+    }
+    // every QP inverts Iw = R Ib R' (det Iw = det Ib): a singular or non-finite Ib would put 1/0 into the whole batch
+    const double* I = p->trunk_inertia;
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(I[i])) return false;
+    const double det = I[0] * (I[4] * I[8] - I[5] * I[7]) - I[1] * (I[3] * I[8] - I[5] * I[6]) +
+                       I[2] * (I[3] * I[7] - I[4] * I[6]);
+    return det > 0.0;
 }
 
 // staging block sizes of the host-pointer path (bytes)

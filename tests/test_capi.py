@@ -69,6 +69,48 @@ def test_create_rejects_bad_arguments():
     assert lib.lmpc_solve_batch_device(None, None, None, 1, None, None, None, None) == -1
 
 
+def test_create_rejects_unusable_inertia_and_non_finite_weights():
+    """Every QP inverts R Ib R': lmpc_create refuses a trunk inertia with a non-finite entry or without a positive
+    determinant, and non-finite weights or constants, before it touches a device; a full (non-diagonal) symmetric
+    positive definite inertia passes the parameter check."""
+    lib = N.lib()
+    ctx = ctypes.c_void_p()
+
+    def create(edit):
+        p = N.LmpcParams()
+        lib.lmpc_params_go1(ctypes.byref(p))
+        edit(p)
+        rc = lib.lmpc_create(ctypes.byref(p), 10, 1, 0, ctypes.byref(ctx))
+        if rc == 0:
+            lib.lmpc_destroy(ctx)
+        return rc
+
+    def set_field(name, value, index=None):
+        def edit(p):
+            if index is None:
+                setattr(p, name, value)
+            else:
+                getattr(p, name)[index] = value
+        return edit
+
+    for bad in (float("nan"), float("inf")):
+        assert create(set_field("trunk_inertia", bad, 0)) == -1
+        assert create(set_field("trunk_inertia", bad, 5)) == -1  # an off-diagonal entry
+        assert create(set_field("r_weights", bad, 11)) == -1
+        assert create(set_field("q_weights", bad, 3)) == -1
+        for name in ("robot_mass", "mu", "f_max", "gravity", "dt"):
+            assert create(set_field(name, bad)) == -1, name
+    assert create(set_field("trunk_inertia", 0.0, 8)) == -1                     # singular
+    assert create(set_field("trunk_inertia", -0.0158533, 0)) == -1              # negative determinant
+    assert create(lambda p: p.trunk_inertia.__setitem__(slice(0, 9), [0.0] * 9)) == -1
+
+    def full(p):  # symmetric, diagonally dominant
+        p.trunk_inertia[1] = p.trunk_inertia[3] = 0.004
+        p.trunk_inertia[2] = p.trunk_inertia[6] = -0.003
+        p.trunk_inertia[5] = p.trunk_inertia[7] = 0.002
+    assert create(full) in (0, -2)  # LMPC_OK, or LMPC_ERR_DEVICE where there is no GPU: the parameters passed
+
+
 def test_create_without_gpu_fails_cleanly():
     import torch
 

@@ -5,12 +5,16 @@ paths, against the CPU oracle.
 16 QPs per case: states from `synth`, contact arrays built by hand.  Every QP must come back converged and within
 the project's regression guard (TOL_REGRESS = 1e-7, tests/test_gpu_parity.py) of oracle.solve_batch, and the oracle
 must certify every instance (no QP is skipped): the seeds below were picked on the CPU for that.
+
+The cases run with the Go1 preset and, so that the closed-form condensation sees a non-uniform R and a full inertia at
+every shape it distinguishes, with two sets of tests/param_sets.py.
 """
 import functools
 
 import numpy as np
 import pytest
 
+import param_sets as PS
 from conftest import rel_err
 
 from legged_mpc_control_amd import BatchedConvexQPSolver, synth
@@ -49,15 +53,16 @@ CASES = {
 
 
 @functools.lru_cache(maxsize=None)
-def case(name):
-    """-> (params, H, rec, contact, normals, oracle forces); the oracle certifies all NQP instances"""
+def case(name, pset="go1"):
+    """-> (params, H, rec, contact, normals, oracle forces) under the parameter set `pset` (tests/param_sets.py; "go1"
+    is the preset); the oracle certifies all NQP instances"""
     H, con1, tilted, seed = CASES[name]
-    p = synth.params("go1")
+    p = PS.params(pset)
     rec, _ = synth.fill(p, synth.synth_cfg("go1"), H, NQP, seed)
     con = np.ascontiguousarray(np.broadcast_to(con1, (NQP, H, 4)))
     nrm = synth.normals(NQP, seed) if tilted else None
     ref, _, fails = O.solve_batch(O.params_from(p), H, rec, con, n_threads=8, normals=nrm)
-    assert fails == 0, f"{name}: the oracle did not certify {fails} of {NQP} instances"
+    assert fails == 0, f"{name} {pset}: the oracle did not certify {fails} of {NQP} instances"
     ref.setflags(write=False)
     return p, H, rec, con, nrm, ref
 
@@ -79,3 +84,19 @@ def test_condensed_paths_vs_oracle(name, mode):
     print(f"{name} {mode}: max rel err {err:.3e}, status {np.bincount(status)}")
     assert np.all(status == 0), status
     assert err <= TOL_REGRESS, f"{name} {mode}: {err:.3e}"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["ipm", "gi"])
+@pytest.mark.parametrize("pset", ["aniso_r", "everything"])
+@pytest.mark.parametrize("name", list(CASES))
+def test_condensed_paths_general_params(name, pset, mode):
+    """Every shape again off the presets: per-leg, per-component r (the input Hessian block R' diag(r) R has
+    off-diagonal entries on tilted terrain) and, under `everything`, a full trunk inertia and weights on yaw, x, y."""
+    p, H, rec, con, nrm, ref = case(name, pset)
+    s = BatchedConvexQPSolver(p, H, max_batch=NQP, dense_path=mode)
+    grf, status, iters = s.solve(rec, con, normals=nrm)
+    err = rel_err(grf, ref)
+    print(f"{name} {pset} {mode}: max rel err {err:.3e}, status {np.bincount(status)}")
+    assert np.all(status == 0), status
+    assert err <= TOL_REGRESS, f"{name} {pset} {mode}: {err:.3e}"

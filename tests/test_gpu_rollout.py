@@ -52,11 +52,12 @@ def robots37():
     return mixed_robots(29, others, seed=37)
 
 
-def run(dev, H, robots, ticks, warm=False, chunks=None, stream=None, solver=None):
-    """-> dict(robots uint8 [B, 656], act uint8 [B, H, 4] or None, and the logs as NumPy [sum(chunks), B, ...])."""
+def run(dev, H, robots, ticks, warm=False, chunks=None, stream=None, solver=None, params=None):
+    """-> dict(robots uint8 [B, 656], act uint8 [B, H, 4] or None, and the logs as NumPy [sum(chunks), B, ...]).
+    params: the LmpcParams of the context made here (default: the Go1 preset)."""
     import torch
 
-    s = solver or BatchedConvexQPSolver(synth.params(), H, max_batch=0)
+    s = solver or BatchedConvexQPSolver(synth.params() if params is None else params, H, max_batch=0)
     d_rb = R.to_device(robots, dev)
     B = d_rb.shape[0]
     act = torch.zeros((B, H, 4), dtype=torch.uint8, device=dev) if warm else None
@@ -75,10 +76,11 @@ def cold37(dev):
     return robots, is_trot, run(dev, 10, robots, 30)
 
 
-def check_ticks(H, robots, is_trot, out, ticks, check):
+def check_ticks(H, robots, is_trot, out, ticks, check, params=None):
     """Every logged u_0 is the oracle's optimum of the logged command's record (ticks in `check`); every logged command
-    is the host tick from the previous robot and the logged u_0 (every tick); the FSM fields bit for bit."""
-    p, cfg = synth.params(), R.cfg_go1()
+    is the host tick from the previous robot and the logged u_0 (every tick); the FSM fields bit for bit.
+    params: the LmpcParams the rollout ran with (default: the Go1 preset)."""
+    p, cfg = synth.params() if params is None else params, R.cfg_go1()
     op = O.params_from(p)
     B = len(robots)
     cmds = R.commands_from(out["cmd_bytes"])
@@ -138,6 +140,32 @@ def test_per_tick_parity_lds_riccati(dev):
     assert s.dense_path == "off" and s.riccati_path == "lds"
     out = run(dev, 20, robots, 15, solver=s)
     check_ticks(20, robots, is_trot, out, 15, range(15))
+
+
+def test_per_tick_parity_general_params(dev):
+    """The loop off the presets (tests/param_sets.py `everything`: per-leg, per-component r, a full trunk inertia,
+    weights on yaw, x and y, mu 0.45, f_max 120): 5 robots, 8 ticks, every tick checked as above, and every logged
+    state against the oracle's own A and B applied to the logged command and u_0 -- not the host build of the device
+    code, whose R Ib R' and 3 x 3 inverse the presets' diagonal inertia never exercised in full."""
+    import param_sets as PS
+
+    p = PS.params("everything")
+    op = O.params_from(p)
+    robots, is_trot = mixed_robots(3, [(F.CRAWL, (0.2, 0.0), 0.1), (F.STAND, (0.0, 0.0), 0.0)], seed=51)
+    B, ticks = len(robots), 8
+    out = run(dev, 10, robots, ticks, params=p)
+    check_ticks(10, robots, is_trot, out, ticks, range(ticks), params=p)
+    cv = R.commands_view(out["cmd_bytes"])
+    worst = 0.0
+    for t in range(ticks):
+        for b in range(B):
+            c = cv[t, b]
+            x = np.concatenate([c["euler"], c["pos"], c["omega"], c["vel"]])
+            want = RR.plant_step(op, x, c["rot"].reshape(3, 3), c["foot_abs"], out["u0"][t, b])
+            worst = max(worst, rel_err(out["x"][t, b], want))
+    print(f"logged x vs the oracle's plant step: max rel err {worst:.2e}")
+    assert worst <= 1e-12
+    assert np.abs(out["u0"]).max() > 1.0  # forces were applied
 
 
 def test_warm_start_carried_on_the_device(dev, cold37):

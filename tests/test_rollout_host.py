@@ -151,6 +151,42 @@ def test_plant_step_is_the_qp_stage_0_transition():
         assert rb.tick == 1
 
 
+def test_closed_loop_general_params():
+    """The host tick off the presets (tests/param_sets.py `everything`: a full trunk inertia among the rest): 5 robots
+    (3 trot, 1 crawl, 1 stand), H = 10, 8 ticks of host advance + the oracle's exact solve.  Every plant step equals
+    the oracle's own A and B applied to the command's state, rotation and feet and the applied u_0, to 1e-12 -- with
+    the presets' diagonal inertia six of the nine products per row of R Ib and (R Ib) R' vanish."""
+    import param_sets as PS
+
+    H, ticks = 10, 8
+    p, cfg = PS.params("everything"), R.cfg_go1()
+    op = O.params_from(p)
+    rng = np.random.default_rng(51)
+    specs = [(F.TROT, (rng.uniform(-0.6, 0.6), rng.uniform(-0.3, 0.3)), rng.uniform(-0.5, 0.5)) for _ in range(3)]
+    specs += [(F.CRAWL, (0.2, 0.0), 0.1), (F.STAND, (0.0, 0.0), 0.0)]
+    steps = 0
+    for gait, vd, yr in specs:
+        x0 = standing(rng.uniform(-3.0, 3.0))
+        x0[0:2] = rng.uniform(-0.05, 0.05, 2)  # roll and pitch: R is a full rotation, not Rz alone
+        rb = R.robot_init(cfg, x0, vd, yr, 0.30, gait, 4.0)
+        u0 = None
+        for t in range(ticks):
+            if u0 is not None:
+                st = rb.cmd.state
+                want = RR.plant_step(op, R.robot_state(rb), np.array(st.root_rot_mat).reshape(3, 3),
+                                     np.array(st.foot_pos_abs), u0)
+            R.advance(p, cfg, rb, u0)  # the plant step with the previous u_0, then the book-keeping
+            if u0 is not None:
+                assert close(R.robot_state(rb), want, 1e-12), (gait, t)
+                steps += 1
+            rec, con = synth.command_to_record(p, H, rb.cmd)
+            grf, _, _ = O.solve(op, H, rec, con)  # raises unless the oracle solve succeeds
+            u0 = grf[0]
+            assert np.abs(u0).max() > 1.0
+        assert rb.tick == ticks - 1
+    assert steps == 5 * (ticks - 1)
+
+
 def test_cpu_closed_loop_trot_tracks_its_command():
     """Host advance + the oracle's exact solve, one Go1 trot robot from standing at 0.30: H = 10, 200 ticks, command
     (0.5, 0.1) m/s and 0.3 rad/s.  The caps are conditions (the NumPy-only prototype: height within 0.0024 m,

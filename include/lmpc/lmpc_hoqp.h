@@ -39,6 +39,10 @@
 extern "C" {
 #endif
 
+/* 2: the warm entry points (lmpc_hoqp_solve_*_warm, lmpc_hoqp_act_len), lmpc_hoqp_options.warm_rounds appended
+ * (in the struct's former tail padding: its size is unchanged, and 0 there means the default), lmpc_hoqp_abi_version itself */
+#define LMPC_HOQP_ABI_VERSION 2
+
 #define LMPC_HOQP_MAX_LEVELS 4
 #define LMPC_HOQP_MAX_VARS 64
 #define LMPC_HOQP_MAX_ROWS 64      /* equality or inequality rows of one level */
@@ -61,6 +65,9 @@ typedef struct {
                            each level's answer is the active-set optimum qpOASES returns, to rounding;
                            0 = the interior-point iterate as is (about 13 % faster on the WBC; ~1e-9 instead of
                            ~1e-12 there, ~1e-4 on degenerate levels) */
+    int32_t warm_rounds; /* ABI 2, warm entry points only: repair rounds the crossover may spend on a carried active
+                           set before the level falls back to its cold solve; 1..12, default 12 (the cold crossover's
+                           own budget); 0 = the default */
 } lmpc_hoqp_options;
 
 typedef struct lmpc_hoqp_ctx lmpc_hoqp_ctx;
@@ -76,6 +83,7 @@ int64_t lmpc_hoqp_record_len(const lmpc_hoqp_dims* d);
  * rounded up to 16 (the WBC: 40 448 B, four chains per CU); sets how many chains share a CU */
 int64_t lmpc_hoqp_lds_bytes(const lmpc_hoqp_dims* d);
 int lmpc_hoqp_slack_len(const lmpc_hoqp_dims* d); /* total inequality rows */
+int lmpc_hoqp_abi_version(void);
 
 int lmpc_hoqp_create(const lmpc_hoqp_dims* d, int max_batch, int device, lmpc_hoqp_ctx** out);
 void lmpc_hoqp_destroy(lmpc_hoqp_ctx* ctx);
@@ -112,6 +120,32 @@ int lmpc_hoqp_solve_batch_z(lmpc_hoqp_ctx* ctx, const double* tasks, int batch, 
                             int32_t* status, int32_t* iters, double* z, int32_t* zcols);
 int lmpc_hoqp_solve_device_z(lmpc_hoqp_ctx* ctx, const double* d_tasks, int batch, double* d_x, double* d_slack,
                              int32_t* d_status, int32_t* d_iters, double* d_z, int32_t* d_zcols, void* stream);
+
+/* ---- Warm start (ABI 2) ---------------------------------------------------------------------------------------
+ * The same solves, each level first trying the active set the chain's previous solve left.  `act` is one opaque
+ * block of lmpc_hoqp_act_len(dims) 64-bit words per chain ([batch][act_len], < 0 = LMPC_ERR_ARG for dimensions
+ * outside the limits), read and written in place; the caller keeps it between calls and zero-fills it to say "no
+ * set" (first call, a reset, another robot in that slot).  Per level it holds a validity bit and, for each of the up
+ * to LMPC_HOQP_MAX_STACKED stacked rows, the two flags of the exact crossover's final classification: frozen
+ * (higher-level) row active, own row violated.
+ * A level with a valid set runs that crossover from y = 0 on the carried flags -- frozen rows whose projection this
+ * call's null-space basis annihilates are taken out first -- for at most options.warm_rounds repair rounds.  If the
+ * result verifies (multipliers, row sides and stationarity to 1e-9 of the level's scale, the test of the cold
+ * crossover) it is the level's active-set optimum and the level costs no interior-point iteration; otherwise, and for
+ * a level without a valid set, the level is solved exactly as lmpc_hoqp_solve_* solves it.  A carried set can
+ * therefore cost time, never the answer; with a zero-filled block the results are the cold entry points' bit for bit.
+ * Written back, always: the set the level's crossover verified (warm or cold), or "no set" for a level that kept its
+ * interior-point iterate and for every level of a LMPC_QP_NAN chain.
+ * Iteration word (iters[b][l]): bits 0-15 interior-point iterations and bits 16-17 the crossover (1 tried, 3 taken) as
+ * above; bit 18 = a carried set was tried; bit 19 = it was taken (then bits 0-15 are 0, bits 16-17 are 3 and bits
+ * 20-23 hold the repair rounds it needed).  The cold entry points never set bits 18-23.
+ * act == NULL is LMPC_ERR_ARG.  Stream and ordering rules: those of lmpc_hoqp_solve_device.  The stacked Z matrices
+ * (the _z calls) are not returned here. */
+int64_t lmpc_hoqp_act_len(const lmpc_hoqp_dims* d);
+int lmpc_hoqp_solve_batch_warm(lmpc_hoqp_ctx* ctx, const double* tasks, int batch, double* x, double* slack,
+                               int32_t* status, int32_t* iters, uint64_t* act);
+int lmpc_hoqp_solve_device_warm(lmpc_hoqp_ctx* ctx, const double* d_tasks, int batch, double* d_x, double* d_slack,
+                                int32_t* d_status, int32_t* d_iters, uint64_t* d_act, void* stream);
 
 /* ---- WBC task formulation (wbc.cpp:102-259), the step before the hierarchical QP ----------------------------
  * Per robot, the dynamics terms the reference takes from Pinocchio (wbc.cpp:59-91) and the task targets; the

@@ -45,7 +45,10 @@ HOQP_SYMBOLS = (
     "lmpc_hoqp_lds_bytes", "lmpc_hoqp_create", "lmpc_hoqp_destroy", "lmpc_hoqp_set_options", "lmpc_hoqp_solve_batch",
     "lmpc_hoqp_solve_device", "lmpc_hoqp_sync", "lmpc_wbc_tasks", "lmpc_wbc_tasks_device",
     "lmpc_hoqp_solve_batch_z", "lmpc_hoqp_solve_device_z",
+    # ABI 2: warm start from the last solve's active sets
+    "lmpc_hoqp_abi_version", "lmpc_hoqp_act_len", "lmpc_hoqp_solve_batch_warm", "lmpc_hoqp_solve_device_warm",
 )
+HOQP_ABI_VERSION = 2
 HOQP_MAX_LEVELS = 4
 # include/lmpc/lmpc_multi.h: one process, several GPUs (liblmpc_multi.so, RCCL scatter / gather)
 MULTI_LIB_PATH = os.path.join(_HERE, "lib", "liblmpc_multi.so")
@@ -214,7 +217,7 @@ class LmpcHoqpDims(ctypes.Structure):
 
 class LmpcHoqpOptions(ctypes.Structure):
     _fields_ = [("max_iter", ctypes.c_int32), ("tol_mu", ctypes.c_double), ("tol_res", ctypes.c_double),
-                ("crossover", ctypes.c_int32)]
+                ("crossover", ctypes.c_int32), ("warm_rounds", ctypes.c_int32)]
 
 
 class LmpcWbcInput(ctypes.Structure):
@@ -468,6 +471,13 @@ def lib():
         L.lmpc_hoqp_solve_device_z.restype = ctypes.c_int
         L.lmpc_hoqp_sync.argtypes = [vp]
         L.lmpc_hoqp_sync.restype = ctypes.c_int
+        L.lmpc_hoqp_abi_version.restype = ctypes.c_int
+        L.lmpc_hoqp_act_len.argtypes = [hdp]
+        L.lmpc_hoqp_act_len.restype = ctypes.c_int64
+        L.lmpc_hoqp_solve_batch_warm.argtypes = [vp, dp, ctypes.c_int, dp, dp, i32p, i32p, ctypes.POINTER(ctypes.c_uint64)]
+        L.lmpc_hoqp_solve_batch_warm.restype = ctypes.c_int
+        L.lmpc_hoqp_solve_device_warm.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp]
+        L.lmpc_hoqp_solve_device_warm.restype = ctypes.c_int
         L.lmpc_wbc_tasks.argtypes = [ctypes.POINTER(LmpcWbcInput), dp]
         L.lmpc_wbc_tasks.restype = ctypes.c_int
         L.lmpc_wbc_tasks_device.argtypes = [vp, ctypes.c_int, vp, vp]
@@ -618,6 +628,9 @@ def lib():
                                      f"{L.lmpc_robot_size()} B, this binding is ABI {ROLLOUT_ABI_VERSION} / {ROBOT_BYTES} B")
         # exactly this ABI, diagnostic builds (LMPC_LIB) included: the command and options structs above are ABI-7
         # layouts, and an older library would read their fields at the wrong offsets without an error
+        if L.lmpc_hoqp_abi_version() != HOQP_ABI_VERSION:
+            raise NativeLibraryError(f"{path}: lmpc_hoqp.h ABI {L.lmpc_hoqp_abi_version()}, this binding is ABI "
+                                     f"{HOQP_ABI_VERSION}")
         if L.lmpc_abi_version() != ABI_VERSION:
             raise NativeLibraryError(f"{path}: ABI version {L.lmpc_abi_version()}, this binding is ABI {ABI_VERSION}")
         _lib = L

@@ -13,7 +13,8 @@
 
 namespace lmpc {
 hipError_t launch_hoqp(const HoqpDev& P, const double* rec, int batch, double* x, double* w, int32_t* status,
-                       int32_t* iters, double* zout, int32_t* zcols, double* scratch, hipStream_t stream);
+                       int32_t* iters, double* zout, int32_t* zcols, double* scratch, unsigned long long* act,
+                       hipStream_t stream);
 }
 
 struct lmpc_hoqp_ctx {
@@ -28,6 +29,7 @@ struct lmpc_hoqp_ctx {
     size_t scratch_inst = 0;
     double* d_z = nullptr;      // host path staging: stacked Z matrices + column counts (allocated on first use)
     int32_t* d_zc = nullptr;
+    unsigned long long* d_act = nullptr;  // host path staging: active-set blocks (allocated on first warm use)
     // orders launches that share d_scratch across streams: recorded on the last launch's stream only when the next
     // one comes on another stream (as lmpc_capi.cpp, round 6: back-to-back launches on one stream pay no event);
     // host-side waits (scratch growth, lmpc_hoqp_sync, lmpc_hoqp_destroy) wait for the device instead
@@ -104,6 +106,8 @@ void fill_dev(lmpc::HoqpDev& P, const lmpc_hoqp_dims* d) {
     P.tol_mu = o.tol_mu;
     P.tol_res = o.tol_res;
     P.crossover = o.crossover;
+    P.warm_rounds = o.warm_rounds;
+    P.act_len = lmpc::HQ_ACT_WORDS * P.L;
 }
 
 hipError_t ensure_scratch(lmpc_hoqp_ctx* c, int batch) {
@@ -130,7 +134,7 @@ bool stream_ok(hipStream_t s, int dev) {
 }
 
 hipError_t launch(lmpc_hoqp_ctx* c, const double* rec, int batch, double* x, double* w, int32_t* st, int32_t* it,
-                  double* z, int32_t* zc, hipStream_t s) {
+                  double* z, int32_t* zc, unsigned long long* act, hipStream_t s) {
     hipError_t e = ensure_scratch(c, batch);
     if (e != hipSuccess) return e;
     if (c->pend && c->last != s) {
@@ -142,7 +146,7 @@ hipError_t launch(lmpc_hoqp_ctx* c, const double* rec, int batch, double* x, dou
     }
     if (!(c->pend && c->last == s) && c->ev_live && c->ev_stream != s && (e = hipStreamWaitEvent(s, c->ev, 0)) != hipSuccess)
         return e;
-    e = lmpc::launch_hoqp(c->P, rec, batch, x, w, st, it, z, zc, c->d_scratch, s);
+    e = lmpc::launch_hoqp(c->P, rec, batch, x, w, st, it, z, zc, c->d_scratch, act, s);
     if (e != hipSuccess) return e;
     c->last = s;
     c->pend = true;
@@ -170,6 +174,7 @@ void lmpc_hoqp_options_default(lmpc_hoqp_options* o) {
     o->tol_mu = 1e-13;
     o->tol_res = 1e-7;
     o->crossover = 1;
+    o->warm_rounds = 12;  // LMPC_HQ_XO_ROUNDS (lmpc_hoqp.hip)
 }
 
 int64_t lmpc_hoqp_lds_bytes(const lmpc_hoqp_dims* d) {
@@ -187,6 +192,13 @@ int64_t lmpc_hoqp_record_len(const lmpc_hoqp_dims* d) {
     for (int l = 0; l < d->num_levels; ++l) len += (int64_t)(d->eq_rows[l] + d->ineq_rows[l]) * (d->num_vars + 1);
     return len;
 }
+
+int64_t lmpc_hoqp_act_len(const lmpc_hoqp_dims* d) {
+    if (!dims_ok(d)) return LMPC_ERR_ARG;
+    return (int64_t)lmpc::HQ_ACT_WORDS * d->num_levels;
+}
+
+int lmpc_hoqp_abi_version(void) { return LMPC_HOQP_ABI_VERSION; }
 
 int lmpc_hoqp_slack_len(const lmpc_hoqp_dims* d) {
     if (!dims_ok(d)) return LMPC_ERR_ARG;
@@ -235,6 +247,7 @@ void lmpc_hoqp_destroy(lmpc_hoqp_ctx* c) {
     (void)hipFree(c->d_scratch);
     (void)hipFree(c->d_z);
     (void)hipFree(c->d_zc);
+    (void)hipFree(c->d_act);
     if (c->ev) (void)hipEventDestroy(c->ev);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -242,18 +255,19 @@ void lmpc_hoqp_destroy(lmpc_hoqp_ctx* c) {
 
 int lmpc_hoqp_set_options(lmpc_hoqp_ctx* c, const lmpc_hoqp_options* o) {
     if (!c || !o || o->max_iter < 1 || !(o->tol_mu > 0.0) || !(o->tol_res > 0.0) || o->crossover < 0 ||
-        o->crossover > 1)
+        o->crossover > 1 || o->warm_rounds < 0 || o->warm_rounds > 12)
         return LMPC_ERR_ARG;
     c->P.max_iter = o->max_iter;
     c->P.tol_mu = o->tol_mu;
     c->P.tol_res = o->tol_res;
     c->P.crossover = o->crossover;
+    c->P.warm_rounds = o->warm_rounds ? o->warm_rounds : 12;  // 0: an initialiser from before the field existed
     return LMPC_OK;
 }
 
-int lmpc_hoqp_solve_batch_z(lmpc_hoqp_ctx* c, const double* tasks, int batch, double* x, double* slack,
-                            int32_t* status, int32_t* iters, double* z, int32_t* zcols) {
-    if (!c || batch < 0 || batch > c->max_batch) return LMPC_ERR_ARG;
+// the host-pointer solves: act != NULL = the warm instantiation, its blocks staged in and out
+static int solve_batch_impl(lmpc_hoqp_ctx* c, const double* tasks, int batch, double* x, double* slack,
+                            int32_t* status, int32_t* iters, double* z, int32_t* zcols, uint64_t* act) {
     if (batch == 0) return LMPC_OK;
     if (!tasks || !x || (!slack && c->P.slack_len > 0)) return LMPC_ERR_ARG;
     DeviceScope scope(c->device);
@@ -267,6 +281,11 @@ int lmpc_hoqp_solve_batch_z(lmpc_hoqp_ctx* c, const double* tasks, int batch, do
             c->d_z = nullptr;
             return LMPC_ERR_ALLOC;
         }
+    }
+    const size_t nact = (size_t)batch * c->P.act_len * sizeof(uint64_t);
+    if (act && !c->d_act && hipMalloc(&c->d_act, (size_t)c->max_batch * c->P.act_len * sizeof(uint64_t)) != hipSuccess) {
+        c->d_act = nullptr;
+        return LMPC_ERR_ALLOC;
     }
     double* d_x = c->d_out;
     double* d_w = c->d_out + nx;
@@ -282,8 +301,9 @@ int lmpc_hoqp_solve_batch_z(lmpc_hoqp_ctx* c, const double* tasks, int batch, do
     if (hipMemcpyAsync(c->d_rec, tasks, (size_t)batch * c->P.rec_len * sizeof(double), hipMemcpyHostToDevice, s) !=
         hipSuccess)
         return LMPC_ERR_DEVICE;
-    if (launch(c, c->d_rec, batch, d_x, d_w, d_status, d_iters, z ? c->d_z : nullptr, z ? c->d_zc : nullptr, s) !=
-        hipSuccess)
+    if (act && hipMemcpyAsync(c->d_act, act, nact, hipMemcpyHostToDevice, s) != hipSuccess) return LMPC_ERR_DEVICE;
+    if (launch(c, c->d_rec, batch, d_x, d_w, d_status, d_iters, z ? c->d_z : nullptr, z ? c->d_zc : nullptr,
+               act ? c->d_act : nullptr, s) != hipSuccess)
         return LMPC_ERR_LAUNCH;
     bool ok = hipMemcpyAsync(x, d_x, nx * sizeof(double), hipMemcpyDeviceToHost, s) == hipSuccess;
     if (nw) ok = ok && hipMemcpyAsync(slack, d_w, nw * sizeof(double), hipMemcpyDeviceToHost, s) == hipSuccess;
@@ -297,8 +317,21 @@ int lmpc_hoqp_solve_batch_z(lmpc_hoqp_ctx* c, const double* tasks, int batch, do
     if (z && zcols)
         ok = ok && hipMemcpyAsync(zcols, c->d_zc, (size_t)batch * c->P.L * sizeof(int32_t), hipMemcpyDeviceToHost, s) ==
                        hipSuccess;
+    if (act) ok = ok && hipMemcpyAsync(act, c->d_act, nact, hipMemcpyDeviceToHost, s) == hipSuccess;
     ok = ok && hipStreamSynchronize(s) == hipSuccess;
     return ok ? LMPC_OK : LMPC_ERR_DEVICE;
+}
+
+int lmpc_hoqp_solve_batch_z(lmpc_hoqp_ctx* c, const double* tasks, int batch, double* x, double* slack,
+                            int32_t* status, int32_t* iters, double* z, int32_t* zcols) {
+    if (!c || batch < 0 || batch > c->max_batch) return LMPC_ERR_ARG;
+    return solve_batch_impl(c, tasks, batch, x, slack, status, iters, z, zcols, nullptr);
+}
+
+int lmpc_hoqp_solve_batch_warm(lmpc_hoqp_ctx* c, const double* tasks, int batch, double* x, double* slack,
+                               int32_t* status, int32_t* iters, uint64_t* act) {
+    if (!c || batch < 0 || batch > c->max_batch || !act) return LMPC_ERR_ARG;
+    return solve_batch_impl(c, tasks, batch, x, slack, status, iters, nullptr, nullptr, act);
 }
 
 int lmpc_hoqp_solve_batch(lmpc_hoqp_ctx* c, const double* tasks, int batch, double* x, double* slack,
@@ -316,8 +349,25 @@ int lmpc_hoqp_solve_device_z(lmpc_hoqp_ctx* c, const double* d_tasks, int batch,
     hipStream_t s = (hipStream_t)stream;
     if (!stream_ok(s, c->device)) return LMPC_ERR_ARG;
     double* w = d_slack ? d_slack : c->d_out;  // no inequality rows: the kernel writes no slack
-    return launch(c, d_tasks, batch, d_x, w, d_status, d_iters, d_z, d_zcols, s) == hipSuccess ? LMPC_OK
-                                                                                                  : LMPC_ERR_LAUNCH;
+    return launch(c, d_tasks, batch, d_x, w, d_status, d_iters, d_z, d_zcols, nullptr, s) == hipSuccess
+               ? LMPC_OK
+               : LMPC_ERR_LAUNCH;
+}
+
+int lmpc_hoqp_solve_device_warm(lmpc_hoqp_ctx* c, const double* d_tasks, int batch, double* d_x, double* d_slack,
+                                int32_t* d_status, int32_t* d_iters, uint64_t* d_act, void* stream) {
+    if (!c || batch < 0 || !d_act) return LMPC_ERR_ARG;
+    if (batch == 0) return LMPC_OK;
+    if (!d_tasks || !d_x || (!d_slack && c->P.slack_len > 0)) return LMPC_ERR_ARG;
+    DeviceScope scope(c->device);
+    if (!scope.ok) return LMPC_ERR_DEVICE;
+    hipStream_t s = (hipStream_t)stream;
+    if (!stream_ok(s, c->device)) return LMPC_ERR_ARG;
+    double* w = d_slack ? d_slack : c->d_out;
+    return launch(c, d_tasks, batch, d_x, w, d_status, d_iters, nullptr, nullptr, (unsigned long long*)d_act, s) ==
+                   hipSuccess
+               ? LMPC_OK
+               : LMPC_ERR_LAUNCH;
 }
 
 int lmpc_hoqp_solve_device(lmpc_hoqp_ctx* c, const double* d_tasks, int batch, double* d_x, double* d_slack,

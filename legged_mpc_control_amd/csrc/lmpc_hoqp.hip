@@ -857,7 +857,9 @@ __device__ __attribute__((noinline)) double nnls_rows(const HS& S_, int ls, int 
     return lam;
 }
 
-template <int NP>
+// WARM (the warm instantiation's attempt on a carried set, below): the rounds are capped by warm_rounds instead, and
+// the number of repair rounds a verified set needed is left in S.pv[0].
+template <int NP, bool WARM = false>
 __device__ __attribute__((noinline)) bool crossover(const HoqpDev& P_, const HS& S_, int p, int nr, int nd, double bd0,
                                                     double bd1, int fl0, int fl1, double scale, const gdouble* Hg,
                                                     gdouble* Tg, int lane) {
@@ -883,7 +885,8 @@ __device__ __attribute__((noinline)) bool crossover(const HoqpDev& P_, const HS&
         const int r = lane + 64 * k;
         tyi[k] = r < nr ? row_dot<NP>(S, ls, nd, r, S.y) : 0.0;
     }
-    for (int rd = 0; rd < LMPC_HQ_XO_ROUNDS; ++rd) {
+    const int rounds = WARM ? uni(P_.warm_rounds) : LMPC_HQ_XO_ROUNDS;
+    for (int rd = 0; rd < rounds; ++rd) {
         // weights of K_A and the correction's right-hand side: rhs - K_A y_i = -c - Hy y_i + R' (w (bd - R y_i))
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
@@ -1070,6 +1073,7 @@ __device__ __attribute__((noinline)) bool crossover(const HoqpDev& P_, const HS&
         if (lane < nd) st = hy_dot<NP>(P, Hg, S.dy, nd, lane) + S.c[lane] + rt_dot(S, ls, nr, S.q, lane);
         if (__any(!(fabs(st) <= tol) || !(y == y))) { HQ_XO_FAIL(3); return false; }  // NaN fails every comparison
         if (lane < np) S.y[lane] = lane < nd ? y : 0.0;
+        if (WARM && lane == 0) S.pv[0] = rd;
         LMPC_SYNC();
         HQ_XO_FAIL(0);
         return true;
@@ -1087,12 +1091,20 @@ struct Rows {
 
 }  // namespace
 
-template <int NP>
+// WARM: the warm instantiation (lmpc_hoqp_solve_device_warm).  `act` holds P.act_len 64-bit words per chain,
+// HQ_ACT_WORDS per level: word 0 bit 0 = the level's set is valid, words 1-2 = bit 0 of the crossover's final flags
+// (frozen row active) of rows 0..63 and 64..127, words 3-4 = bit 1 (own row violated).  A level with a valid set
+// starts the crossover from y = 0 on those flags and the true bounds; a verified answer ends the level without an
+// interior-point iteration, anything else runs the cold level below unchanged.  Every level's words are written back:
+// the set its crossover verified, or zeros.  The cold instantiation reads and writes no block and compiles to the
+// code it had before the warm one existed (every warm branch is `if constexpr`).
+template <int NP, bool WARM>
 __global__ void __launch_bounds__(64) lmpc_hoqp_kernel(const HoqpDev P, const double* __restrict__ recs,
                                                        double* __restrict__ xout, double* __restrict__ wout,
                                                        int32_t* __restrict__ status, int32_t* __restrict__ iters,
                                                        double* __restrict__ zout, int32_t* __restrict__ zcols,
-                                                       double* __restrict__ scratch, int batch) {
+                                                       double* __restrict__ scratch, int batch,
+                                                       unsigned long long* act) {
     extern __shared__ __attribute__((aligned(16))) double hq_smem[];
     const int b = blockIdx.x;
     if (b >= batch) return;
@@ -1145,6 +1157,7 @@ __global__ void __launch_bounds__(64) lmpc_hoqp_kernel(const HoqpDev P, const do
         LMPC_SYNC();
         Rows W;
         double bmax = 0.0;
+        int dropm = 0;  // warm: bit k = this lane's row lane + 64 k was dropped
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             const int r = lane + 64 * k;
@@ -1164,6 +1177,7 @@ __global__ void __launch_bounds__(64) lmpc_hoqp_kernel(const HoqpDev P, const do
                     if (rmx <= 1e-12 * dmx * zmax) {
                         for (int j = 0; j < P.np; ++j) S.R[r * ls + j] = 0.0;
                         a = 1.0;
+                        if constexpr (WARM) dropm |= 1 << k;
                     }
                 }
                 W.bd[k] = a;
@@ -1215,7 +1229,35 @@ __global__ void __launch_bounds__(64) lmpc_hoqp_kernel(const HoqpDev P, const do
 #ifdef LMPC_HQ_ITDIAG
         int it_p0 = 0;
 #endif
-        for (int pass = two_pass ? 0 : 1; pass < 2; ++pass) {
+        // ---- warm: the carried active set, from y = 0 (S.y, above), on the true bounds -------------------------
+        int wbits = 0;  // iteration word bit 18: a carried set was tried, bit 19: taken, bits 20-23: its repair rounds
+        unsigned long long* al = nullptr;
+        if constexpr (WARM) {
+            al = act + ((int64_t)b * P.act_len + (int64_t)HQ_ACT_WORDS * l);
+            if (P.crossover && nr > 0 && nd > 0 && (al[0] & 1ull)) {
+                int fl[2];
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const int r = lane + 64 * k;
+                    const bool act_in = (al[1 + k] >> lane) & 1ull, vio_in = (al[3 + k] >> lane) & 1ull;
+                    fl[k] = 0;
+                    // a frozen row this tick's projection dropped (zero row, h = 1) binds nothing
+                    if (r < p) fl[k] = (act_in && !((dropm >> k) & 1)) ? 1 : 0;
+                    else if (r < nr) fl[k] = vio_in ? 2 : 0;
+                }
+                exact = crossover<NP, true>(P, S, p, nr, nd, hb_true[0], hb_true[1], fl[0], fl[1], scale, Hg, Tg, lane);
+                wbits = 1 << 18;
+                if (exact) {
+                    xo = 3;
+                    any_exact = true;
+                    wbits |= (1 << 19) | ((uni(S.pv[0]) & 15) << 20);
+                } else {  // the cold level starts as it does without an attempt (S.y is still zero)
+                    if (lane < P.np) S.dy[lane] = 0.0;
+                    LMPC_SYNC();
+                }
+            }
+        }
+        for (int pass = (WARM && exact) ? 2 : (two_pass ? 0 : 1); pass < 2; ++pass) {
             const double tmu = pass == 0 ? LMPC_HQ_XO_TOL : P.tol_mu;
             for (;; ++it) {
                 // residuals: r_d = H x + c + C'z, r_p = C x + slack - d
@@ -1418,6 +1460,26 @@ __global__ void __launch_bounds__(64) lmpc_hoqp_kernel(const HoqpDev P, const do
             if (exact || nonfin || numstop || it >= P.max_iter || !(nr > 0 && nd > 0)) break;
         }
         const bool xo_verified = exact;
+        if constexpr (WARM) {
+            // the verified set = the weights of the crossover's last round (S.wh: non-zero on an active frozen row and
+            // on a violated own row), untouched since; a level that kept its iterate leaves no set
+            unsigned long long a0 = 0, a1 = 0, v0 = 0, v1 = 0;
+            if (xo_verified) {
+                const bool f0 = lane < nr && S.wh[lane] != 0.0;
+                const bool f1 = lane + 64 < nr && S.wh[lane + 64] != 0.0;
+                a0 = __ballot(f0 && lane < p);
+                a1 = __ballot(f1 && lane + 64 < p);
+                v0 = __ballot(f0 && lane >= p);
+                v1 = __ballot(f1 && lane + 64 >= p);
+            }
+            if (lane == 0) {
+                al[0] = xo_verified ? 1ull : 0ull;
+                al[1] = a0;
+                al[2] = a1;
+                al[3] = v0;
+                al[4] = v1;
+            }
+        }
         exact = exact || clean;
         // LMPC_QP_CONVERGED: the clean stop, a verified crossover, or -- documented in lmpc_hoqp.h -- the relaxed
         // degenerate stop (complementarity 1e3 below its tolerance, residuals within 1e3 of theirs); a level left on
@@ -1441,7 +1503,7 @@ __global__ void __launch_bounds__(64) lmpc_hoqp_kernel(const HoqpDev P, const do
         if (lane == 0 && iters && b < 65536 && l == P.L - 1) lmpc_hq_xo_reason[b] = lmpc_hq_nnls[b];
         if (iters && lane == 0) iters[(int64_t)b * P.L + l] = it | (xo << 16) | (it_p0 << 20) | (xr << 28);
 #else
-        if (iters && lane == 0) iters[(int64_t)b * P.L + l] = it | (xo << 16);
+        if (iters && lane == 0) iters[(int64_t)b * P.L + l] = it | (xo << 16) | wbits;
 #endif
         // ---- outputs: w_l = max(0, D_l Z y - g) for the final y, x += Z y ------------------------------
 #pragma unroll
@@ -1504,6 +1566,8 @@ __global__ void __launch_bounds__(64) lmpc_hoqp_kernel(const HoqpDev P, const do
             for (int64_t e = lane; e < (int64_t)P.L * P.n * P.n; e += 64) zout[(int64_t)b * P.L * P.n * P.n + e] = 0.0;
             if (zcols && lane < P.L) zcols[(int64_t)b * P.L + lane] = 0;
         }
+        if constexpr (WARM)  // no set survives a chain that returns zeros
+            for (int e = lane; e < P.act_len; e += 64) act[(int64_t)b * P.act_len + e] = 0ull;
         st = 2;
     }
     if (status && lane == 0) status[b] = st;
@@ -1528,31 +1592,43 @@ extern "C" int lmpc_debug_hoqp_substamps(unsigned long long* out, int n) {
 }
 #endif
 
-hipError_t launch_hoqp(const HoqpDev& P, const double* rec, int batch, double* x, double* w, int32_t* status,
-                       int32_t* iters, double* zout, int32_t* zcols, double* scratch, hipStream_t stream) {
-    if (batch <= 0) return hipSuccess;
+namespace {
+template <bool WARM>
+hipError_t launch_hoqp_t(const HoqpDev& P, const double* rec, int batch, double* x, double* w, int32_t* status,
+                         int32_t* iters, double* zout, int32_t* zcols, double* scratch, unsigned long long* act,
+                         hipStream_t stream) {
     const size_t lds = hq_lds_doubles(P) * sizeof(double);
     switch (P.np) {
         case 16:
-            hipLaunchKernelGGL(lmpc_hoqp_kernel<16>, dim3(batch), dim3(64), lds, stream, P, rec, x, w, status, iters,
-                               zout, zcols, scratch, batch);
+            hipLaunchKernelGGL((lmpc_hoqp_kernel<16, WARM>), dim3(batch), dim3(64), lds, stream, P, rec, x, w, status,
+                               iters, zout, zcols, scratch, batch, act);
             break;
         case 32:
-            hipLaunchKernelGGL(lmpc_hoqp_kernel<32>, dim3(batch), dim3(64), lds, stream, P, rec, x, w, status, iters,
-                               zout, zcols, scratch, batch);
+            hipLaunchKernelGGL((lmpc_hoqp_kernel<32, WARM>), dim3(batch), dim3(64), lds, stream, P, rec, x, w, status,
+                               iters, zout, zcols, scratch, batch, act);
             break;
         case 48:
-            hipLaunchKernelGGL(lmpc_hoqp_kernel<48>, dim3(batch), dim3(64), lds, stream, P, rec, x, w, status, iters,
-                               zout, zcols, scratch, batch);
+            hipLaunchKernelGGL((lmpc_hoqp_kernel<48, WARM>), dim3(batch), dim3(64), lds, stream, P, rec, x, w, status,
+                               iters, zout, zcols, scratch, batch, act);
             break;
         case 64:
-            hipLaunchKernelGGL(lmpc_hoqp_kernel<64>, dim3(batch), dim3(64), lds, stream, P, rec, x, w, status, iters,
-                               zout, zcols, scratch, batch);
+            hipLaunchKernelGGL((lmpc_hoqp_kernel<64, WARM>), dim3(batch), dim3(64), lds, stream, P, rec, x, w, status,
+                               iters, zout, zcols, scratch, batch, act);
             break;
         default:
             return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+}  // namespace
+
+// act == nullptr: the cold instantiation; otherwise the warm one on the chains' active-set blocks (read and written)
+hipError_t launch_hoqp(const HoqpDev& P, const double* rec, int batch, double* x, double* w, int32_t* status,
+                       int32_t* iters, double* zout, int32_t* zcols, double* scratch, unsigned long long* act,
+                       hipStream_t stream) {
+    if (batch <= 0) return hipSuccess;
+    return act ? launch_hoqp_t<true>(P, rec, batch, x, w, status, iters, zout, zcols, scratch, act, stream)
+               : launch_hoqp_t<false>(P, rec, batch, x, w, status, iters, zout, zcols, scratch, nullptr, stream);
 }
 
 }  // namespace lmpc

@@ -9,6 +9,7 @@
 namespace lmpc {
 
 constexpr int HQ_MAX_LEVELS = 4;
+constexpr int HQ_ACT_WORDS = 5;  // 64-bit words of one level's carried active set (lmpc_hoqp.hip, warm instantiation)
 
 struct HoqpDev {
     int n;                   // decision variables
@@ -26,6 +27,8 @@ struct HoqpDev {
     double tol_mu, tol_res;
     int crossover;           // 1: exact active-set crossover after each level's interior point (lmpc_hoqp.hip)
     int64_t scratch_len;     // doubles of global scratch per instance: Z, Z' (n x np), Hy and the crossover's T (np x np)
+    int warm_rounds;         // warm instantiation: repair rounds of the crossover on a carried set
+    int act_len;             // warm instantiation: 64-bit words of one chain's active-set block (HQ_ACT_WORDS * L)
 };
 
 __host__ __device__ inline int hq_ls(const HoqpDev& P) { return P.np + 1; }  // LDS row stride (odd: rows fall on different banks)

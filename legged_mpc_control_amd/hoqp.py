@@ -108,6 +108,7 @@ class HoqpBatch:
         self.levels = dims.num_levels
         self.rec_len = record_len(dims)
         self.slack_len = int(self._L.lmpc_hoqp_slack_len(ctypes.byref(dims)))
+        self.act_len = int(self._L.lmpc_hoqp_act_len(ctypes.byref(dims)))  # 64-bit words of one chain's warm block
         self._ctx = ctypes.c_void_p()
         # a context is not thread-safe (lmpc_hoqp.h) and ctypes releases the GIL during a call: every call that
         # uses it (staging buffers, stream, event) holds this lock
@@ -126,7 +127,7 @@ class HoqpBatch:
         except Exception:
             pass
 
-    def set_options(self, max_iter=None, tol_mu=None, tol_res=None, crossover=None):
+    def set_options(self, max_iter=None, tol_mu=None, tol_res=None, crossover=None, warm_rounds=None):
         o = N.LmpcHoqpOptions()
         self._L.lmpc_hoqp_options_default(ctypes.byref(o))
         if crossover is not None:
@@ -137,15 +138,27 @@ class HoqpBatch:
             o.tol_mu = tol_mu
         if tol_res is not None:
             o.tol_res = tol_res
+        if warm_rounds is not None:
+            o.warm_rounds = int(warm_rounds)
         with self._lock:
             N.check(self._L.lmpc_hoqp_set_options(self._ctx, ctypes.byref(o)), "lmpc_hoqp_set_options")
 
-    def solve(self, records: np.ndarray, with_z: bool = False):
+    def solve(self, records: np.ndarray, with_z: bool = False, act: Optional[np.ndarray] = None):
         """Host path.  records [B][rec_len] -> x [B][levels][n], slack [B][total ineq rows], status [B],
         iters [B][levels]; with_z: also z [B][levels][n][n] and zcols [B][levels], every level's
-        getStackedZMatrix() in the first zcols columns (lmpc_hoqp_solve_batch_z)."""
+        getStackedZMatrix() in the first zcols columns (lmpc_hoqp_solve_batch_z).
+
+        act (int64 or uint64 [B][act_len], zeros = no set): the warm solve (lmpc_hoqp_solve_batch_warm) from the
+        chains' carried active sets; the updated blocks (a new array, same dtype) are returned as a fifth value."""
         rec = np.ascontiguousarray(records, dtype=np.float64).reshape(-1, self.rec_len)
         B = rec.shape[0]
+        if act is not None:
+            if with_z:
+                raise ValueError("the warm solve returns no stacked Z matrices")
+            act = np.asarray(act)
+            if act.dtype not in (np.dtype(np.int64), np.dtype(np.uint64)) or act.shape != (B, self.act_len):
+                raise ValueError(f"act: expected int64 [{B}][{self.act_len}], got {act.dtype} {act.shape}")
+            act = np.array(act, order="C")  # a copy: written in place by the call
         x = np.zeros((B, self.levels, self.n))
         w = np.zeros((B, max(self.slack_len, 1)))
         st = np.zeros(B, dtype=np.int32)
@@ -153,6 +166,14 @@ class HoqpBatch:
         dp, i32p = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)
         z = np.zeros((B, self.levels, self.n, self.n)) if with_z else None
         zc = np.zeros((B, self.levels), dtype=np.int32) if with_z else None
+        if act is not None:
+            with self._lock:
+                N.check(self._L.lmpc_hoqp_solve_batch_warm(self._ctx, rec.ctypes.data_as(dp), B, x.ctypes.data_as(dp),
+                                                           w.ctypes.data_as(dp), st.ctypes.data_as(i32p),
+                                                           it.ctypes.data_as(i32p),
+                                                           act.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))),
+                        "lmpc_hoqp_solve_batch_warm")
+            return x, w[:, :self.slack_len], st, it, act
         with self._lock:
             N.check(self._L.lmpc_hoqp_solve_batch_z(self._ctx, rec.ctypes.data_as(dp), B, x.ctypes.data_as(dp),
                                                     w.ctypes.data_as(dp), st.ctypes.data_as(i32p),
@@ -164,9 +185,12 @@ class HoqpBatch:
             return x, w[:, :self.slack_len], st, it, z, zc
         return x, w[:, :self.slack_len], st, it
 
-    def solve_device(self, d_rec, d_x, d_w, d_status=None, d_iters=None, stream=None, d_z=None, d_zcols=None):
+    def solve_device(self, d_rec, d_x, d_w, d_status=None, d_iters=None, stream=None, d_z=None, d_zcols=None,
+                     d_act=None):
         """Device path on torch tensors (resident in HBM), asynchronous on `stream` (default: torch's current);
-        d_z [B][levels][n][n] / d_zcols [B][levels]: every level's getStackedZMatrix() (optional)."""
+        d_z [B][levels][n][n] / d_zcols [B][levels]: every level's getStackedZMatrix() (optional).
+        d_act int64 [B][act_len] (zeros = no set): the warm solve (lmpc_hoqp_solve_device_warm), the blocks read and
+        written in place; not together with d_z."""
         import torch
 
         s = stream if stream is not None else torch.cuda.current_stream(self.device)
@@ -186,6 +210,15 @@ class HoqpBatch:
                 raise ValueError("d_zcols needs d_z")
             check_device_tensor("d_zcols", d_zcols, torch.int32, (B, self.levels), dev)
         ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        if d_act is not None:
+            if d_z is not None:
+                raise ValueError("the warm solve returns no stacked Z matrices (d_act with d_z)")
+            check_device_tensor("d_act", d_act, torch.int64, (B, self.act_len), dev)
+            with self._lock:
+                N.check(self._L.lmpc_hoqp_solve_device_warm(self._ctx, ptr(d_rec), B, ptr(d_x), ptr(d_w), ptr(d_status),
+                                                            ptr(d_iters), ptr(d_act), ctypes.c_void_p(s.cuda_stream)),
+                        "lmpc_hoqp_solve_device_warm")
+            return
         with self._lock:
             N.check(self._L.lmpc_hoqp_solve_device_z(self._ctx, ptr(d_rec), B, ptr(d_x), ptr(d_w), ptr(d_status),
                                                      ptr(d_iters), ptr(d_z), ptr(d_zcols),

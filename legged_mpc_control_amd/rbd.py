@@ -181,9 +181,13 @@ def compute_device(model, d_state, d_terms, stream=None):
 class WbcPipeline:
     """state -> lmpc_wbc_input -> WBC records -> hierarchical QP, device-resident, on one stream.
 
-    The intermediate buffers (inputs, records, every level's x, slacks) are allocated once for `max_batch` robots."""
+    The intermediate buffers (inputs, records, every level's x, slacks) are allocated once for `max_batch` robots.
 
-    def __init__(self, model: N.LmpcRbdModel, max_batch: int, device: int = 0):
+    warm=True: the hierarchical solve starts every level from the active set the robot's previous solve left
+    (lmpc_hoqp_solve_device_warm).  The pipeline owns the blocks (`d_act`, zeroed = no set); `reset_warm()` zeroes
+    them, and so does a call with another batch size (the rows then belong to other robots)."""
+
+    def __init__(self, model: N.LmpcRbdModel, max_batch: int, device: int = 0, warm: bool = False):
         import torch
 
         if max_batch < 1:
@@ -201,6 +205,16 @@ class WbcPipeline:
         self.d_slack = torch.empty((self.max_batch, max(self.solver.slack_len, 1)), dtype=torch.float64, device=dev)
         self.d_status = torch.empty(self.max_batch, dtype=torch.int32, device=dev)
         self.d_iters = torch.empty((self.max_batch, dims.num_levels), dtype=torch.int32, device=dev)
+        self.warm = bool(warm)
+        self.d_act = None
+        self._warm_batch = 0
+        if self.warm:
+            self.d_act = torch.zeros((self.max_batch, self.solver.act_len), dtype=torch.int64, device=dev)
+
+    def reset_warm(self):
+        """Forget every robot's carried active sets: the next solve is a cold one."""
+        if self.d_act is not None:
+            self.d_act.zero_()
 
     def close(self):
         self.solver.close()
@@ -217,6 +231,13 @@ class WbcPipeline:
         s = stream if stream is not None else torch.cuda.current_stream(self.device)
         wbc_inputs_device(self.model, d_state, d_target, self.d_inputs[:B], s)
         records_device(self.d_inputs[:B], self.d_records[:B], s)
+        d_act = None
+        if self.warm:
+            if B != self._warm_batch:
+                with torch.cuda.stream(s):
+                    self.d_act.zero_()
+                self._warm_batch = B
+            d_act = self.d_act[:B]
         self.solver.solve_device(self.d_records[:B], self.d_levels[:B], self.d_slack[:B], self.d_status[:B],
-                                 self.d_iters[:B], s)
+                                 self.d_iters[:B], s, d_act=d_act)
         return self.d_levels[:B, -1], self.d_status[:B]

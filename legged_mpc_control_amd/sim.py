@@ -152,9 +152,11 @@ class WbcSim:
     (state -> torques), then `lmpc_sim_step_device` with tau read by stride from the pipeline's x and the candidate
     contacts by stride from the targets -- on one stream, with no host synchronisation in between."""
 
-    def __init__(self, model: N.LmpcRbdModel, max_batch: int, c: N.LmpcSimCfg = None, device: int = 0, contact=None):
+    def __init__(self, model: N.LmpcRbdModel, max_batch: int, c: N.LmpcSimCfg = None, device: int = 0, contact=None,
+                 warm: bool = False):
         """contact: an `lmpc_contact_cfg` (contact.cfg(...)) steps the plant with the frictional contact model
-        (`lmpc_contact_step_device`, the targets' contacts as its mask) and `c` is not used; None: the present plant."""
+        (`lmpc_contact_step_device`, the targets' contacts as its mask) and `c` is not used; None: the present plant.
+        warm: `WbcPipeline(warm=True)`, every tick's hierarchical solve starts from the last tick's active sets."""
         import torch
 
         self.model = model
@@ -162,7 +164,7 @@ class WbcSim:
         self.contact = contact
         self.max_batch = int(max_batch)
         self.device = device
-        self.pipeline = WbcPipeline(model, max_batch, device)
+        self.pipeline = WbcPipeline(model, max_batch, device, warm=warm)
         self.d_out = torch.empty((self.max_batch, OUT_BYTES), dtype=torch.uint8, device=torch.device("cuda", device))
 
     def close(self):
@@ -171,7 +173,8 @@ class WbcSim:
     def run_device(self, d_state, d_target, ticks: int, substeps: int = 1, log: bool = False, stream=None):
         """`ticks` controller ticks of cfg.dt * substeps each; d_state (uint8 [B][288]) is updated in place.  The
         targets stay as given.  log=True -> dict of device tensors, one row per tick: states uint8 [ticks][B][288]
-        (after the tick), held / touch int32 [ticks][B][4], wbc_status / sim_status int32 [ticks][B]."""
+        (after the tick), held / touch int32 [ticks][B][4], wbc_status / sim_status int32 [ticks][B], x float64
+        [ticks][B][42] (the tick's WBC solution) and wbc_iters int32 [ticks][B][3] (its iteration words)."""
         import torch
 
         B = int(d_state.shape[0]) if d_state.dim() >= 1 else -1
@@ -190,7 +193,10 @@ class WbcSim:
                         held=torch.empty((ticks, B, 4), dtype=torch.int32, device=dev),
                         touch=torch.empty((ticks, B, 4), dtype=torch.int32, device=dev),
                         wbc_status=torch.empty((ticks, B), dtype=torch.int32, device=dev),
-                        sim_status=torch.empty((ticks, B), dtype=torch.int32, device=dev))
+                        sim_status=torch.empty((ticks, B), dtype=torch.int32, device=dev),
+                        x=torch.empty((ticks, B, self.pipeline.d_levels.shape[2]), dtype=torch.float64, device=dev),
+                        wbc_iters=torch.empty((ticks, B, self.pipeline.d_iters.shape[1]), dtype=torch.int32,
+                                              device=dev))
             flags = d_out.view(torch.int32)[:, OUT_BYTES // 4 - 10:]  # held (4), touch (4), status, reserved
         with torch.cuda.stream(s):
             for t in range(ticks):
@@ -204,6 +210,8 @@ class WbcSim:
                     C.step_device(self.model, self.contact, d_state, d_x[:, TAU_OFFSET:TAU_OFFSET + 12], d_contact,
                                   d_state, d_out, None, substeps, s)
                 if log:
+                    logs["x"][t].copy_(d_x)
+                    logs["wbc_iters"][t].copy_(self.pipeline.d_iters[:B])
                     logs["states"][t].copy_(d_state)
                     logs["held"][t].copy_(flags[:, 0:4])
                     logs["touch"][t].copy_(flags[:, 4:8])

@@ -205,7 +205,7 @@ class StackLoop:
     def __init__(self, model: N.LmpcRbdModel, params: N.LmpcParams, horizon: int, max_batch: int,
                  rollout_cfg: N.LmpcRolloutCfg, sim_cfg: N.LmpcSimCfg, wbc_per_mpc: int, substeps: int = 1,
                  template: N.LmpcWbcTarget = None, device: int = 0, estimator: N.LmpcEstCfg = None,
-                 plant: N.LmpcContactCfg = None, plant_split: bool = False):
+                 plant: N.LmpcContactCfg = None, plant_split: bool = False, wbc_warm: bool = False):
         """estimator: an `lmpc_est_cfg` (est.cfg(dt=...)) closes the loop on the Kalman filter's estimate instead of the
         plant's own state; its dt must be the low-level tick's, substeps * sim_cfg.dt.  None: the plant's state is the
         feedback, exactly as without this option.
@@ -214,7 +214,10 @@ class StackLoop:
         (`lmpc_contact_step_device`) instead of `lmpc_sim_step_device`: every foot is in the mask on every step, so the
         candidate rule and its launch are gone; its dt and ground_z must be sim_cfg's.  None: the present plant,
         exactly as without this option.  plant_split: run that step in its three-launch form on a workspace the loop
-        owns (the same bits; DESIGN.md 4h has the timings of both)."""
+        owns (the same bits; DESIGN.md 4h has the timings of both).
+
+        wbc_warm: the WBC solves start from the active sets of the robot's previous low-level tick
+        (`WbcPipeline(warm=True)`; DESIGN.md 4c "Warm start").  False: cold solves, exactly as without this option."""
         import torch
 
         if max_batch < 1:
@@ -236,7 +239,7 @@ class StackLoop:
         dev = torch.device("cuda", device)
         self.solver = BatchedConvexQPSolver(params, self.H, max_batch=0, device=device)
         N.check(N.lib().lmpc_stack_reserve(self.solver._ctx, self.max_batch), "lmpc_stack_reserve")
-        self.pipeline = WbcPipeline(model, self.max_batch, device)
+        self.pipeline = WbcPipeline(model, self.max_batch, device, warm=wbc_warm)
         self.d_grf = torch.zeros((self.max_batch, self.H, 12), dtype=torch.float64, device=dev)
         self.d_qp_status = torch.zeros(self.max_batch, dtype=torch.int32, device=dev)
         self.d_qp_iters = torch.zeros(self.max_batch, dtype=torch.int32, device=dev)
@@ -293,7 +296,7 @@ class StackLoop:
         `qp_iters` int32 [T][B], `target` uint8 [T][B][352].  Per low-level tick k = t * wbc_per_mpc + i: `states`
         uint8 [K][B][288] and `out` uint8 [K][B][472] (after the plant step; `held`, `touch` int32 [K][B][4] and
         `sim_status` int32 [K][B] are views of it), `tau` float64 [K][B][12], `candidates` int32 [K][B][4],
-        `wbc_status` int32 [K][B].  With an estimator also, per low-level tick: `sensors` uint8 [K][B][296], `state_est`
+        `wbc_status` int32 [K][B], `wbc_iters` int32 [K][B][3] (the iteration words of lmpc_hoqp.h).  With an estimator also, per low-level tick: `sensors` uint8 [K][B][296], `state_est`
         uint8 [K][B][288], `filter` uint8 [K][B][2744] (x and P after the update; est.filter_view), `est_out` uint8
         [K][B][312] (`est_status` int32 [K][B] is a view of it), `shadow` uint8 [K][B][472]; and `filter0`,
         `state_est0`, `shadow0` [B][...]: the estimator as this call found it.  `states` and `out` stay the TRUE ones;
@@ -332,7 +335,8 @@ class StackLoop:
                         out=torch.empty((K, B, S.OUT_BYTES), dtype=torch.uint8, device=dev),
                         tau=torch.empty((K, B, 12), dtype=torch.float64, device=dev),
                         candidates=torch.empty((K, B, 4), dtype=torch.int32, device=dev),
-                        wbc_status=torch.empty((K, B), dtype=torch.int32, device=dev))
+                        wbc_status=torch.empty((K, B), dtype=torch.int32, device=dev),
+                        wbc_iters=torch.empty((K, B, self.pipeline.d_iters.shape[1]), dtype=torch.int32, device=dev))
             if plant is not None:
                 logs["contact_out"] = torch.empty((K, B, C.OUT_BYTES), dtype=torch.uint8, device=dev)
             if est is not None:
@@ -377,6 +381,7 @@ class StackLoop:
                         logs["tau"][k].copy_(d_tau)
                         logs["candidates"][k].copy_(d_cand)
                         logs["wbc_status"][k].copy_(d_wst)
+                        logs["wbc_iters"][k].copy_(self.pipeline.d_iters[:B])
                         if plant is not None:
                             logs["contact_out"][k].copy_(d_cout)
                         if est is not None:

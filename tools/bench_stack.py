@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the full loop (include/lmpc/lmpc_stack.h: MPC -> WBC -> rigid-body plant) on MI355X.
 
-    python tools/bench_stack.py [--ticks T] [--repeats R] [--out FILE]
+    python tools/bench_stack.py [--ticks T] [--repeats R] [--out FILE] [--wbc-warm] [--batches 1024,4096] [--whole-only]
 
 1024 and 4096 Go1 trot robots from a standing pose with seeded commands, H = 10, the reference's rates (10 ms MPC tick,
 8 low-level ticks of 1.25 ms).  One HIP event pair around a whole `StackLoop.run_device` of T MPC ticks, after a
@@ -15,6 +15,11 @@ warm-up run from the same start; the best of R repeats.  In the same process, fr
 
 glue_us_per_mpc_tick = the whole - solve_only - the 8 replayed wbc_sim ticks: the advance launch (which also expands
 the records), the targets launch and the 8 candidate launches, with their host calls.  Prints ONE JSON line.
+
+--wbc-warm: `StackLoop(..., wbc_warm=True)`, every timed run from zeroed active-set blocks; the row gains `wbc_warm`:
+the share of WBC levels tried and taken warm after the first low-level tick, the mean repair rounds of the taken ones
+and the mean interior-point iterations per level, from the warm-up run's `wbc_iters`.  --whole-only: the whole loop's
+time alone (the A/B of the option needs no parts).
 """
 from __future__ import annotations
 
@@ -74,6 +79,9 @@ def main():
     ap.add_argument("--ticks", type=int, default=50)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--wbc-warm", action="store_true")
+    ap.add_argument("--batches", default=",".join(str(b) for b in BATCHES))
+    ap.add_argument("--whole-only", action="store_true")
     args = ap.parse_args()
     import torch
 
@@ -82,9 +90,10 @@ def main():
     dev = torch.device("cuda:0")
     T = args.ticks
     rows = []
-    for batch in BATCHES:
+    for batch in [int(b) for b in args.batches.split(",")]:
         p, cfg, model = synth.params(), rollout.cfg_go1(), rbd.model_go1()
-        loop = stack.StackLoop(model, p, H, batch, cfg, sim.cfg(dt=SIM_DT, ground_z=0.0), WBC_PER_MPC)
+        loop = stack.StackLoop(model, p, H, batch, cfg, sim.cfg(dt=SIM_DT, ground_z=0.0), WBC_PER_MPC,
+                               wbc_warm=args.wbc_warm)
         start = [torch.from_numpy(a).to(dev) for a in start_of(batch, 4000 + batch)]
         bufs = [a.clone() for a in start]
         log = loop.run_device(*bufs, T, log=True)  # warm-up, and the record of what the run does
@@ -96,14 +105,28 @@ def main():
                    fallen=int(((x[:, :, 1].abs() > 0.5) | (x[:, :, 2].abs() > 0.5) |
                                (x[:, :, 5] < 0.5 * x[0, :, 5])).any(dim=0).sum()))
         cmds = log["cmd"].contiguous()
+        it = log["wbc_iters"].cpu().numpy()
+        row["wbc_ipm_iters_per_level_mean"] = [float(v) for v in (it & 0xFFFF).mean(axis=(0, 1))]
+        if args.wbc_warm:
+            taken, tried = (it[1:] >> 19) & 1, (it[1:] >> 18) & 1
+            rounds = ((it[1:] >> 20) & 15)[taken == 1]
+            row["wbc_warm"] = dict(tried_share=float(tried.mean()), taken_share=float(taken.mean()),
+                                   taken_share_per_level=[float(v) for v in taken.mean(axis=(0, 1))],
+                                   repair_rounds_mean=float(rounds.mean()) if rounds.size else 0.0,
+                                   repair_rounds_max=int(rounds.max()) if rounds.size else 0)
 
         def whole():
             for d, s in zip(bufs, start):
                 d.copy_(s)
+            loop.pipeline.reset_warm()
             loop.run_device(*bufs, T)
 
         ms = timed(whole, args.repeats)
         row["whole"] = dict(ms_per_mpc_tick=ms / T, robot_ticks_per_s=batch * T / (ms * 1e-3))
+        if args.whole_only:
+            rows.append(row)
+            loop.close()
+            continue
         grf = torch.empty((batch, H, 12), dtype=torch.float64, device=dev)
         solver = BatchedConvexQPSolver(p, H, max_batch=0)
 

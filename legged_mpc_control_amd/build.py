@@ -159,6 +159,10 @@ TEST_VARIANTS = {
     # the dense polish with every round refactorised (no range-space updates): tests/test_gpu_kkt.py checks that the
     # product's updates reach the same iteration words and forces
     "noschur": (["LMPC_POLISH_SCHUR=0"], ("lmpc_dense.hip", "lmpc_lq.hip", "lmpc_fused.hip")),
+    # the dense path's diagonal tiles by diag_inverse (T and W = L^-1 in tiles of their own, two MFMAs per pivot) in
+    # place of diag_inverse_merged: tests/test_gpu_dense_diag.py checks that the merged tile leaves every bit of the
+    # answers where it was
+    "diag2tile": (["LMPC_DIAG_TWO_TILES"], ("lmpc_dense.hip", "lmpc_lq.hip", "lmpc_fused.hip")),
 }
 
 

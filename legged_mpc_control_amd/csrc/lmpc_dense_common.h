@@ -557,6 +557,86 @@ static __device__ __attribute__((always_inline)) DiagInv diag_inverse(ldouble* s
     return out;
 }
 
+// ---------------------------------------------------------------------------
+// diag_inverse with T and W in one tile, for the interior-point / polish kernel (lmpc_dense_kernel.h); bit for bit
+// diag_inverse's results.  At pivot block o the trailing update of T touches columns > o+2 only and that of W
+// columns <= o+2 only (W = L^-1 is lower triangular and its rows from o on are still those of I to the right of
+// column o-1), so one tile X holds both -- columns that have had their pivot are W's, the others T's -- and one MFMA
+// updates both: its A operand is W's (-L_C below the pivot, unit rows in it), its B operand row c of L_C where
+// column c is still T's and column c of L_p^-1 W_p where it is W's, W_p = I on the pivot columns themselves.  Every
+// element sees the products it saw in its own tile.  Per pivot that is one MFMA, one LDS round trip and one
+// substitution chain instead of two of each: a lone wave pays ~80 cycles per fp64 MFMA and the fp64 VALU does not
+// run beside it (profiles/r01_ubench_latency.log, profiles/overlap/), so the second MFMA was pure chain length.
+// What the shared tile costs: the pivot columns are cleared with the pivot rows ahead of the MFMA (T's entries
+// there are spent, W's start from zero), and the pivot rows collect L_C' to the right of the pivot -- the strict
+// upper triangle is zeroed once at the end.  The dual active set (lmpc_gi.hip) keeps diag_inverse.
+// ---------------------------------------------------------------------------
+static __device__ __attribute__((always_inline)) DiagInv diag_inverse_merged(ldouble* scr, d4 M, int amask, int lane) {
+    amask = __builtin_amdgcn_readfirstlane(amask);  // uniform (tile_mask), but arguments arrive in VGPRs
+    ldouble* sX = scr;        // 128: staging of the registers that hold the pivot rows (as in diag_inverse)
+    ldouble* tr = scr + 256;  // 16 x 17: transpose staging of W
+    const int c = lane & 15, g = lane >> 4;
+    d4 X = M;
+#pragma unroll
+    for (int blk = 0; blk < 5; ++blk) {
+        if (!((amask >> blk) & 1)) continue;
+        const int o = 3 * blk;
+        const int i0 = o >> 2, i1 = (o + 2) >> 2;
+        const int ra = 4 * i0 + g - o, rb = 4 * i1 + g - o;
+        const bool ina = ra >= 0 && ra < 3, inb = i1 != i0 && rb >= 0 && rb < 3;
+        const bool cp = c >= o && c <= o + 2;  // a pivot column
+        auto so = [&](int a) { return ((o + a) >> 2 == i0 ? 0 : 64) + 16 * ((o + a) & 3); };
+        LMPC_SYNC();
+        sX[lane] = X[i0];
+        if (i1 != i0) sX[64 + lane] = X[i1];
+        // the pivot rows and columns start from zero: the MFMA below writes L_p^-1 W_p into the rows and W's new
+        // columns -L_C L_p^-1 under the pivot
+#pragma unroll
+        for (int i = 0; i < 4; ++i) X[i] = (cp || (i == i0 && ina) || (i == i1 && inb)) ? 0.0 : X[i];
+        LMPC_SYNC();
+        const double p00 = sX[so(0) + o], p10 = sX[so(1) + o], p11 = sX[so(1) + o + 1];
+        const double p20 = sX[so(2) + o], p21 = sX[so(2) + o + 1], p22 = sX[so(2) + o + 2];
+        // row o+a at this lane's column: T[o+a][c] = T[c][o+a] right of the pivot, W[o+a][c] left of it
+        const double r0 = sX[so(0) + c], r1 = sX[so(1) + c], r2 = sX[so(2) + c];
+        // P = L_p L_p' (diag_inverse's arithmetic)
+        const double m11 = fma(p00, p11, -p10 * p10);
+        const double c00 = fma(p11, p22, -p21 * p21), c01 = fma(p10, p22, -p21 * p20), c02 = fma(p10, p21, -p11 * p20);
+        const double det = fma(p00, c00, fma(-p10, c01, p20 * c02));
+        const double i00 = rsq_nr(p00), q1 = rsq_nr(m11), q2 = rsq_nr(det);
+        const double l10 = p10 * i00, l20 = p20 * i00;
+        const double i11 = (p00 * i00) * q1;
+        const double l21 = fma(-l20, l10, p21) * i11;
+        const double i22 = (m11 * q1) * q2;
+        // L_p^-1 applied to this lane's column of the pivot rows (W_p = I on the pivot columns): row c of L_C right of
+        // the pivot, column c of L_p^-1 W_p from the pivot leftwards
+        const double s0 = cp ? (c == o ? 1.0 : 0.0) : r0;
+        const double s1 = cp ? (c == o + 1 ? 1.0 : 0.0) : r1;
+        const double s2 = cp ? (c == o + 2 ? 1.0 : 0.0) : r2;
+        const double y0 = s0 * i00;
+        const double y1 = fma(-l10, y0, s1) * i11;
+        const double y2 = fma(-l21, y1, fma(-l20, y0, s2)) * i22;
+        const double ys = g == 0 ? y0 : g == 1 ? y1 : y2;
+        const double bv = g < 3 ? ys : 0.0;
+        const double av = c > o + 2 ? bv : 0.0;
+        const double aw = cp ? (g == c - o ? 1.0 : 0.0) : -av;
+        X = MFMA64(aw, bv, X);
+    }
+    // W = L^-1 is X's lower triangle: uit = W; ui = W' through LDS (column stride 17: distinct banks)
+    d4 W;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) W[i] = 4 * i + g >= c ? X[i] : 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) tr[c * 17 + 4 * i + g] = W[i];
+    LMPC_SYNC();
+    DiagInv out;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        out.uit[i] = W[i];
+        out.ui[i] = tr[(4 * i + g) * 17 + c];
+    }
+    return out;
+}
+
 
 // Coupled-block masks of a factorisation's four tiles, computed once ahead of the tile loop: bit b = leg-step b is
 // valid (b < nls) and coupled (bit b of `coupled`: all ones in the interior point and the dual active set, the

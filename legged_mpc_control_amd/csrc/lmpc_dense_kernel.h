@@ -476,7 +476,11 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
                 if (b >= NT) continue;
                 DSTAMP(4);
                 if (b >= keep_tiles) {
+#ifndef LMPC_DIAG_TWO_TILES
+                    const DiagInv di = diag_inverse_merged(S.scr, Tl[tix(b, b)], tile_mask(tmasks, b), lane);
+#else  // the test-only "diag2tile" build (tests/test_gpu_dense_diag.py): T and W in tiles of their own
                     const DiagInv di = diag_inverse(S.scr, Tl[tix(b, b)], tile_mask(tmasks, b), lane);
+#endif
                     Ui[b] = di.ui;
                     UiT[b] = di.uit;
                 }

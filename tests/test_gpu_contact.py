@@ -55,6 +55,20 @@ def vec(st):
     return np.frombuffer(bytes(st), dtype=np.float64)
 
 
+def lifted_states(md, seed, count=67, ground_z=0.0):
+    """`count` states of make_sim_states(md, seed), each lifted so that one of its feet lies on the ground z = ground_z,
+    0.1 mm above or below it, or 2 mm below it; the torques; and the masks (all ones on two robots of three)."""
+    states, taus = make_sim_states(md, seed, count)
+    masks = []
+    for i, s in enumerate(states):
+        zs = np.sort(R.terms(md, s)["foot_pos"][2::3])
+        s[5] -= zs[i % 4] + [0.0, 1e-4, -1e-4, -2e-3][(i // 4) % 4]
+        if ground_z != 0.0:
+            s[5] += ground_z
+        masks.append((1, 1, 1, 1) if i % 3 else PATTERNS[(5 * i + 7) % 16])
+    return states, taus, masks
+
+
 @pytest.fixture(scope="module")
 def pool():
     """Per robot: 67 states, torques and masks; per configuration the host's step (and three-substep step) and the
@@ -64,12 +78,7 @@ def pool():
     out = {}
     for r, name in enumerate(("go1", "a1")):
         md, m = model_json(name), preset(name)
-        states, taus = make_sim_states(md, 950 + r, 67)
-        masks = []
-        for i, s in enumerate(states):
-            zs = np.sort(R.terms(md, s)["foot_pos"][2::3])
-            s[5] -= zs[i % 4] + [0.0, 1e-4, -1e-4, -2e-3][(i // 4) % 4]
-            masks.append((1, 1, 1, 1) if i % 3 else PATTERNS[(5 * i + 7) % 16])
+        states, taus, masks = lifted_states(md, 950 + r)
         st = [rbd.state_from_vector(s) for s in states]
         p = dict(model=m, states=st, taus=np.array(taus), masks=np.array(masks, dtype=np.int32), cfg={}, step={},
                  step3={}, K={}, c={}, ref={})

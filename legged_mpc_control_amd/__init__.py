@@ -7,12 +7,12 @@ include/lmpc/lmpc.h.
 """
 from . import _native
 from ._native import (GAIT_CRAWL, GAIT_STAND, GAIT_TROT, GAIT_TROT_WITH_STAND, LmpcCommand, LmpcEstCfg, LmpcEstFilter,
-                      LmpcEstOut, LmpcEstSensors, LmpcLegKin, LmpcOptions, LmpcParams, LmpcRbdModel, LmpcRbdState,
+                      LmpcEstOut, LmpcEstSensors, LmpcLegKin, LmpcLowlevelCfg, LmpcLowlevelOut, LmpcOptions, LmpcParams, LmpcRbdModel, LmpcRbdState,
                       LmpcRbdTerms, LmpcRobot, LmpcRolloutCfg, LmpcRolloutLog, LmpcSimCfg, LmpcSimOut, LmpcStackRobot,
                       LmpcWbcTarget, NativeLibraryError)
 from .solver import (BatchedConvexQPSolver, ConvexQPSolver, LeggedContactFSM, LeggedCtrl, LeggedFeedback,
                      LeggedParam, LeggedState, foot_jacobian, grf_to_torque, leg_kin_default, solver_options)
-from . import est, rbd, rollout, sim, stack, synth
+from . import est, lowlevel, rbd, rollout, sim, stack, synth
 from .rbd import WbcPipeline
 from .sim import WbcSim
 from .stack import StackLoop
@@ -27,4 +27,5 @@ __all__ = [
     "sim", "WbcSim", "LmpcSimCfg", "LmpcSimOut",
     "stack", "StackLoop", "LmpcStackRobot",
     "est", "LmpcEstCfg", "LmpcEstSensors", "LmpcEstFilter", "LmpcEstOut",
+    "lowlevel", "LmpcLowlevelCfg", "LmpcLowlevelOut",
 ]

@@ -99,6 +99,14 @@ CONTACT_SYMBOLS = (
     "lmpc_contact_step_device",
 )
 CONTACT_ABI_VERSION = 1
+# include/lmpc/lmpc_lowlevel.h: the reference's joint-PD low-level controller
+LOWLEVEL_SYMBOLS = (
+    "lmpc_lowlevel_abi_version", "lmpc_lowlevel_cfg_size", "lmpc_lowlevel_out_size", "lmpc_lowlevel_block_robots",
+    "lmpc_lowlevel_cfg_go1", "lmpc_lowlevel_cfg_a1", "lmpc_leg_kin_from_model", "lmpc_leg_fk", "lmpc_leg_inv_kin",
+    "lmpc_lowlevel", "lmpc_lowlevel_device",
+)
+LOWLEVEL_ABI_VERSION = 1
+LL_IK_NAN, LL_VEL_NAN, LL_TAU_NONFINITE, LL_CLAMPED = 1, 2, 4, 8
 
 
 class LmpcParams(ctypes.Structure):
@@ -332,6 +340,20 @@ class LmpcEstOut(ctypes.Structure):
         ("foot_pos_rel", ctypes.c_double * 12), ("foot_pos_world", ctypes.c_double * 12),
         ("foot_vel_world", ctypes.c_double * 12), ("estimated_contacts", ctypes.c_int32 * 4),
         ("status", ctypes.c_int32), ("reserved", ctypes.c_int32),
+    ]
+
+
+class LmpcLowlevelCfg(ctypes.Structure):
+    _fields_ = [
+        ("kin", LmpcLegKin), ("kp", (ctypes.c_double * 3) * 4), ("kd", (ctypes.c_double * 3) * 4),
+        ("tau_limit", ctypes.c_double * 3),
+    ]
+
+
+class LmpcLowlevelOut(ctypes.Structure):
+    _fields_ = [
+        ("tau", ctypes.c_double * 12), ("joint_tau_tgt", ctypes.c_double * 12), ("joint_ang_tgt", ctypes.c_double * 12),
+        ("joint_vel_tgt", ctypes.c_double * 12), ("flags", ctypes.c_int32 * 4),
     ]
 
 
@@ -623,6 +645,29 @@ def lib():
         if L.lmpc_contact_abi_version() != CONTACT_ABI_VERSION or contact_sizes != contact_mirrors:
             raise NativeLibraryError(f"{path}: lmpc_contact.h ABI {L.lmpc_contact_abi_version()} with struct sizes "
                                      f"{contact_sizes}, this binding is ABI {CONTACT_ABI_VERSION} with {contact_mirrors}")
+        lcp, lop = ctypes.POINTER(LmpcLowlevelCfg), ctypes.POINTER(LmpcLowlevelOut)
+        for name in ("lmpc_lowlevel_abi_version", "lmpc_lowlevel_cfg_size", "lmpc_lowlevel_out_size",
+                     "lmpc_lowlevel_block_robots"):
+            getattr(L, name).restype = ctypes.c_int
+        L.lmpc_lowlevel_cfg_go1.argtypes = [lcp]
+        L.lmpc_lowlevel_cfg_go1.restype = None
+        L.lmpc_lowlevel_cfg_a1.argtypes = [lcp]
+        L.lmpc_lowlevel_cfg_a1.restype = None
+        L.lmpc_leg_kin_from_model.argtypes = [mp, kp]
+        L.lmpc_leg_kin_from_model.restype = ctypes.c_int
+        L.lmpc_leg_fk.argtypes = [kp, ctypes.c_int, dp, dp]
+        L.lmpc_leg_fk.restype = ctypes.c_int
+        L.lmpc_leg_inv_kin.argtypes = [kp, ctypes.c_int, dp, dp, dp]
+        L.lmpc_leg_inv_kin.restype = ctypes.c_int
+        L.lmpc_lowlevel.argtypes = [lcp, sp, tp, i32p, lop]
+        L.lmpc_lowlevel.restype = ctypes.c_int
+        L.lmpc_lowlevel_device.argtypes = [lcp, vp, vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int, vp, vp]
+        L.lmpc_lowlevel_device.restype = ctypes.c_int
+        ll_sizes = (L.lmpc_lowlevel_cfg_size(), L.lmpc_lowlevel_out_size())
+        ll_mirrors = (ctypes.sizeof(LmpcLowlevelCfg), ctypes.sizeof(LmpcLowlevelOut))
+        if L.lmpc_lowlevel_abi_version() != LOWLEVEL_ABI_VERSION or ll_sizes != ll_mirrors:
+            raise NativeLibraryError(f"{path}: lmpc_lowlevel.h ABI {L.lmpc_lowlevel_abi_version()} with struct sizes "
+                                     f"{ll_sizes}, this binding is ABI {LOWLEVEL_ABI_VERSION} with {ll_mirrors}")
         if L.lmpc_rollout_abi_version() != ROLLOUT_ABI_VERSION or L.lmpc_robot_size() != ROBOT_BYTES:
             raise NativeLibraryError(f"{path}: lmpc_rollout.h ABI {L.lmpc_rollout_abi_version()} / lmpc_robot of "
                                      f"{L.lmpc_robot_size()} B, this binding is ABI {ROLLOUT_ABI_VERSION} / {ROBOT_BYTES} B")

@@ -45,10 +45,10 @@ SCHED_FLAGS = {
     "lmpc_hoqp.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],
 }
 
-SOURCES = ["lmpc_kernels.hip", "lmpc_lq.hip", "lmpc_fused.hip", "lmpc_dense.hip", "lmpc_gi.hip", "lmpc_prep.hip", "lmpc_rollout.hip", "lmpc_hoqp.hip", "lmpc_wbc.hip", "lmpc_rbd.hip", "lmpc_sim.hip", "lmpc_contact.hip", "lmpc_stack.hip", "lmpc_est.hip", "lmpc_capi.cpp",
+SOURCES = ["lmpc_kernels.hip", "lmpc_lq.hip", "lmpc_fused.hip", "lmpc_dense.hip", "lmpc_gi.hip", "lmpc_prep.hip", "lmpc_rollout.hip", "lmpc_hoqp.hip", "lmpc_wbc.hip", "lmpc_rbd.hip", "lmpc_sim.hip", "lmpc_contact.hip", "lmpc_stack.hip", "lmpc_est.hip", "lmpc_lowlevel.hip", "lmpc_capi.cpp",
            "hoqp_capi.cpp", "lmpc_host.cpp", "ConvexQPSolver.cpp"]
 HEADERS = ["lmpc_device.h", "lmpc_common.h", "lmpc_kernel_common.h", "lmpc_dense_common.h", "lmpc_dense_kernel.h", "lmpc_lq_kernel.h",
-           "lmpc_hoqp_device.h", "lmpc_rbd_common.h", "lmpc_sim_common.h", "lmpc_contact_common.h", "lmpc_quad_device.h", "lmpc_stack_common.h", "lmpc_est_common.h"]
+           "lmpc_hoqp_device.h", "lmpc_rbd_common.h", "lmpc_sim_common.h", "lmpc_contact_common.h", "lmpc_quad_device.h", "lmpc_stack_common.h", "lmpc_est_common.h", "lmpc_lowlevel_common.h"]
 
 
 def hipcc() -> str:
@@ -100,6 +100,7 @@ def build_native(force: bool = False, verbose: bool = False) -> str:
         os.path.join(ROOT, "include", "lmpc", "lmpc_rollout.h"), os.path.join(ROOT, "include", "lmpc", "lmpc_rbd.h"),
         os.path.join(ROOT, "include", "lmpc", "lmpc_sim.h"), os.path.join(ROOT, "include", "lmpc", "lmpc_stack.h"),
         os.path.join(ROOT, "include", "lmpc", "lmpc_est.h"), os.path.join(ROOT, "include", "lmpc", "lmpc_contact.h"),
+        os.path.join(ROOT, "include", "lmpc", "lmpc_lowlevel.h"),
         os.path.join(ROOT, "include", "lmpc", "ConvexQPSolver.hpp"),
         os.path.abspath(__file__)]
     if not force and not _stale(LIB, deps):
@@ -283,6 +284,22 @@ def build_cpp_est_check(force: bool = False) -> str:
     out = os.path.join(ROOT, "tests", "cpp", "build", "est_host_check")
     deps = [src] + [os.path.join(CSRC, h) for h in ("lmpc_est_common.h", "lmpc_rbd_common.h", "lmpc_common.h")] + \
         [os.path.join(ROOT, "include", "lmpc", h) for h in ("lmpc_est.h", "lmpc_sim.h", "lmpc_rbd.h")]
+    if not force and not _stale(out, deps):
+        return out
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    cmd = [host_cxx(), "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+           "-Wno-unknown-pragmas", "-I", os.path.join(ROOT, "include"), "-I", CSRC, "-o", out, src]
+    subprocess.run(cmd, check=True)
+    return out
+
+
+def build_cpp_lowlevel_check(force: bool = False) -> str:
+    """Stand-alone program over csrc/lmpc_lowlevel_common.h (tests/cpp/lowlevel_host_check.cpp), built by the host
+    compiler with AddressSanitizer and UBSan: host code only, no HIP and no liblmpc.so."""
+    src = os.path.join(ROOT, "tests", "cpp", "lowlevel_host_check.cpp")
+    out = os.path.join(ROOT, "tests", "cpp", "build", "lowlevel_host_check")
+    deps = [src] + [os.path.join(CSRC, h) for h in ("lmpc_lowlevel_common.h", "lmpc_common.h")] + \
+        [os.path.join(ROOT, "include", "lmpc", h) for h in ("lmpc_lowlevel.h", "lmpc_sim.h", "lmpc_rbd.h", "lmpc.h")]
     if not force and not _stale(out, deps):
         return out
     os.makedirs(os.path.dirname(out), exist_ok=True)

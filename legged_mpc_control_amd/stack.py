@@ -13,7 +13,9 @@
     state and a shadow `lmpc_sim_out` with the estimate's feet and contact flags, while the plant and the candidate
     rule keep reading the true ones.  With `plant=contact.cfg()` the plant step is `lmpc_contact_step_device` (the
     frictional contact model, include/lmpc/lmpc_contact.h): every foot is in its mask on every step and the candidate
-    launch is gone.
+    launch is gone.  With `low_level=lowlevel.cfg_go1(model)` the low-level tick is the reference's joint-PD controller
+    (`lmpc_lowlevel_device`, include/lmpc/lmpc_lowlevel.h) instead of the whole-body controller: one launch that also
+    writes the candidates, then the plant, which reads the torques from the controller's output block by stride.
 
 What is restated from the reference and what is this library's choice (zero latency, the candidate rule, `touch` as
 the contact flag, the standing mode's foot targets, what a failed stage leaves): include/lmpc/lmpc_stack.h.  The
@@ -28,6 +30,7 @@ import numpy as np
 from . import _native as N
 from . import contact as C
 from . import est as E
+from . import lowlevel as LL
 from . import sim as S
 from .hoqp import check_device_tensor
 from .rbd import STATE_BYTES, TARGET_BYTES, WbcPipeline, target as wbc_target
@@ -199,13 +202,15 @@ def candidates_device(d_sim_out, d_candidates, stream=None):
 class StackLoop:
     """The MPC, the whole-body controller and the plant closed into one device-resident loop.
 
-    Owns an MPC context (cold solves on the context's normal routing), a `WbcPipeline` and the target / candidate /
-    force buffers, all allocated once for `max_batch` robots."""
+    Owns an MPC context (cold solves on the context's normal routing), a `WbcPipeline` (or, with `low_level`, the
+    joint-PD controller's output block) and the target / candidate / force buffers, all allocated once for `max_batch`
+    robots."""
 
     def __init__(self, model: N.LmpcRbdModel, params: N.LmpcParams, horizon: int, max_batch: int,
                  rollout_cfg: N.LmpcRolloutCfg, sim_cfg: N.LmpcSimCfg, wbc_per_mpc: int, substeps: int = 1,
                  template: N.LmpcWbcTarget = None, device: int = 0, estimator: N.LmpcEstCfg = None,
-                 plant: N.LmpcContactCfg = None, plant_split: bool = False, wbc_warm: bool = False):
+                 plant: N.LmpcContactCfg = None, plant_split: bool = False, wbc_warm: bool = False,
+                 low_level: N.LmpcLowlevelCfg = None):
         """estimator: an `lmpc_est_cfg` (est.cfg(dt=...)) closes the loop on the Kalman filter's estimate instead of the
         plant's own state; its dt must be the low-level tick's, substeps * sim_cfg.dt.  None: the plant's state is the
         feedback, exactly as without this option.
@@ -217,9 +222,15 @@ class StackLoop:
         owns (the same bits; DESIGN.md 4h has the timings of both).
 
         wbc_warm: the WBC solves start from the active sets of the robot's previous low-level tick
-        (`WbcPipeline(warm=True)`; DESIGN.md 4c "Warm start").  False: cold solves, exactly as without this option."""
+        (`WbcPipeline(warm=True)`; DESIGN.md 4c "Warm start").  False: cold solves, exactly as without this option.
+
+        low_level: an `lmpc_lowlevel_cfg` (lowlevel.cfg_go1(model)) runs the reference's joint-PD controller in place
+        of the whole-body controller: no `WbcPipeline` is allocated, the template's WBC constants are not read, and
+        `wbc_warm` cannot be combined with it.  None: the whole-body controller, exactly as without this option."""
         import torch
 
+        if low_level is not None and wbc_warm:
+            raise ValueError("wbc_warm warm-starts the whole-body controller, which low_level replaces")
         if max_batch < 1:
             raise ValueError("max_batch must be positive")
         if wbc_per_mpc < 1 or substeps < 1:
@@ -239,7 +250,10 @@ class StackLoop:
         dev = torch.device("cuda", device)
         self.solver = BatchedConvexQPSolver(params, self.H, max_batch=0, device=device)
         N.check(N.lib().lmpc_stack_reserve(self.solver._ctx, self.max_batch), "lmpc_stack_reserve")
-        self.pipeline = WbcPipeline(model, self.max_batch, device, warm=wbc_warm)
+        self.low_level = low_level
+        self.pipeline = WbcPipeline(model, self.max_batch, device, warm=wbc_warm) if low_level is None else None
+        if low_level is not None:
+            self.d_ll_out = torch.zeros((self.max_batch, LL.OUT_BYTES), dtype=torch.uint8, device=dev)
         self.d_grf = torch.zeros((self.max_batch, self.H, 12), dtype=torch.float64, device=dev)
         self.d_qp_status = torch.zeros(self.max_batch, dtype=torch.int32, device=dev)
         self.d_qp_iters = torch.zeros(self.max_batch, dtype=torch.int32, device=dev)
@@ -283,7 +297,8 @@ class StackLoop:
         self._est_batch, self._est_tick = B, 0
 
     def close(self):
-        self.pipeline.close()
+        if self.pipeline is not None:
+            self.pipeline.close()
         self.solver.close()
 
     def run_device(self, d_robots, d_state, d_sim_out, mpc_ticks: int, log: bool = False, stream=None):
@@ -296,7 +311,9 @@ class StackLoop:
         `qp_iters` int32 [T][B], `target` uint8 [T][B][352].  Per low-level tick k = t * wbc_per_mpc + i: `states`
         uint8 [K][B][288] and `out` uint8 [K][B][472] (after the plant step; `held`, `touch` int32 [K][B][4] and
         `sim_status` int32 [K][B] are views of it), `tau` float64 [K][B][12], `candidates` int32 [K][B][4],
-        `wbc_status` int32 [K][B], `wbc_iters` int32 [K][B][3] (the iteration words of lmpc_hoqp.h).  With an estimator also, per low-level tick: `sensors` uint8 [K][B][296], `state_est`
+        `wbc_status` int32 [K][B], `wbc_iters` int32 [K][B][3] (the iteration words of lmpc_hoqp.h); with `low_level`, in
+        place of those two, `ll_out` uint8 [K][B][400] (the controller's lmpc_lowlevel_out; `ll_flags` int32 [K][B][4]
+        is a view of it).  With an estimator also, per low-level tick: `sensors` uint8 [K][B][296], `state_est`
         uint8 [K][B][288], `filter` uint8 [K][B][2744] (x and P after the update; est.filter_view), `est_out` uint8
         [K][B][312] (`est_status` int32 [K][B] is a view of it), `shadow` uint8 [K][B][472]; and `filter0`,
         `state_est0`, `shadow0` [B][...]: the estimator as this call found it.  `states` and `out` stay the TRUE ones;
@@ -316,13 +333,17 @@ class StackLoop:
         T, W = int(mpc_ticks), self.wbc_per_mpc
         d_grf, d_qst, d_qit = self.d_grf[:B], self.d_qp_status[:B], self.d_qp_iters[:B]
         d_target, d_cand = self.d_target[:B], self.d_candidates[:B]
-        est, plant = self.estimator, self.plant
+        est, plant, ll = self.estimator, self.plant, self.low_level
         d_cout = self.d_contact_out[:B] if plant is not None else None
         d_fb_state, d_fb_out = d_state, d_sim_out  # what the advance and the WBC read
+        if est is not None or ll is not None:
+            d_gait = E.gait_view(d_robots)
         if est is not None:
             d_sens, d_filt, d_eout = self.d_sensors[:B], self.d_filter[:B], self.d_est_out[:B]
             d_fb_state, d_fb_out = self.d_state_est[:B], self.d_shadow[:B]
-            d_gait = E.gait_view(d_robots)
+        if ll is not None:
+            d_ll = self.d_ll_out[:B]
+            d_tau = LL.tau_view(d_ll)
         logs = None
         if log:
             K = T * W
@@ -334,9 +355,12 @@ class StackLoop:
                         states=torch.empty((K, B, STATE_BYTES), dtype=torch.uint8, device=dev),
                         out=torch.empty((K, B, S.OUT_BYTES), dtype=torch.uint8, device=dev),
                         tau=torch.empty((K, B, 12), dtype=torch.float64, device=dev),
-                        candidates=torch.empty((K, B, 4), dtype=torch.int32, device=dev),
-                        wbc_status=torch.empty((K, B), dtype=torch.int32, device=dev),
-                        wbc_iters=torch.empty((K, B, self.pipeline.d_iters.shape[1]), dtype=torch.int32, device=dev))
+                        candidates=torch.empty((K, B, 4), dtype=torch.int32, device=dev))
+            if ll is None:
+                logs["wbc_status"] = torch.empty((K, B), dtype=torch.int32, device=dev)
+                logs["wbc_iters"] = torch.empty((K, B, self.pipeline.d_iters.shape[1]), dtype=torch.int32, device=dev)
+            else:
+                logs["ll_out"] = torch.empty((K, B, LL.OUT_BYTES), dtype=torch.uint8, device=dev)
             if plant is not None:
                 logs["contact_out"] = torch.empty((K, B, C.OUT_BYTES), dtype=torch.uint8, device=dev)
             if est is not None:
@@ -361,10 +385,14 @@ class StackLoop:
                     logs["qp_iters"][t].copy_(d_qit)
                     logs["target"][t].copy_(d_target)
                 for i in range(W):
-                    if plant is None:
-                        candidates_device(d_sim_out, d_cand, s)
-                    d_x, d_wst = self.pipeline.solve_device(d_fb_state, d_target, s)
-                    d_tau = d_x[:, S.TAU_OFFSET:S.TAU_OFFSET + 12]
+                    if ll is not None:  # the controller and, for this plant, its candidates: one launch
+                        LL.lowlevel_device(ll, d_fb_state, d_target, d_ll, d_gait, d_sim_out if plant is None else None,
+                                           d_cand if plant is None else None, s)
+                    else:
+                        if plant is None:
+                            candidates_device(d_sim_out, d_cand, s)
+                        d_x, d_wst = self.pipeline.solve_device(d_fb_state, d_target, s)
+                        d_tau = d_x[:, S.TAU_OFFSET:S.TAU_OFFSET + 12]
                     if plant is None:
                         S.step_device(self.model, self.sim_cfg, d_state, d_tau, d_cand, d_state, d_sim_out, self.substeps, s)
                     else:
@@ -380,8 +408,11 @@ class StackLoop:
                         logs["out"][k].copy_(d_sim_out)
                         logs["tau"][k].copy_(d_tau)
                         logs["candidates"][k].copy_(d_cand)
-                        logs["wbc_status"][k].copy_(d_wst)
-                        logs["wbc_iters"][k].copy_(self.pipeline.d_iters[:B])
+                        if ll is None:
+                            logs["wbc_status"][k].copy_(d_wst)
+                            logs["wbc_iters"][k].copy_(self.pipeline.d_iters[:B])
+                        else:
+                            logs["ll_out"][k].copy_(d_ll)
                         if plant is not None:
                             logs["contact_out"][k].copy_(d_cout)
                         if est is not None:
@@ -394,6 +425,8 @@ class StackLoop:
             flags = logs["out"].view(torch.int32)[..., S.OUT_BYTES // 4 - 10:]  # held (4), touch (4), status, reserved
             logs["cmd"] = logs["robots"][..., :N.COMMAND_BYTES]
             logs["held"], logs["touch"], logs["sim_status"] = flags[..., 0:4], flags[..., 4:8], flags[..., 8]
+            if ll is not None:
+                logs["ll_flags"] = LL.flags_view(logs["ll_out"])
             if plant is not None:
                 logs["mode"] = logs["contact_out"].view(torch.int32)[..., C.MODE_OFFSET // 4:C.MODE_OFFSET // 4 + 4]
             if est is not None:

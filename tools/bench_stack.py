@@ -2,6 +2,7 @@
 """Benchmark of the full loop (include/lmpc/lmpc_stack.h: MPC -> WBC -> rigid-body plant) on MI355X.
 
     python tools/bench_stack.py [--ticks T] [--repeats R] [--out FILE] [--wbc-warm] [--batches 1024,4096] [--whole-only]
+                                [--low-level]
 
 1024 and 4096 Go1 trot robots from a standing pose with seeded commands, H = 10, the reference's rates (10 ms MPC tick,
 8 low-level ticks of 1.25 ms).  One HIP event pair around a whole `StackLoop.run_device` of T MPC ticks, after a
@@ -20,6 +21,13 @@ the records), the targets launch and the 8 candidate launches, with their host c
 the share of WBC levels tried and taken warm after the first low-level tick, the mean repair rounds of the taken ones
 and the mean interior-point iterations per level, from the warm-up run's `wbc_iters`.  --whole-only: the whole loop's
 time alone (the A/B of the option needs no parts).
+
+--low-level: `StackLoop(..., low_level=lowlevel.cfg_go1(model))`, the reference's joint-PD controller in place of the
+WBC, beside the WBC loop of the same build from the same start in ALTERNATING timed runs (WBC, low-level, WBC, ...; the
+best of R each).  The row's `lowlevel` holds the whole MPC tick, solve_only as above, and the 8 T low-level ticks
+replayed on the loop's own logged data in two parts: `controller` (lmpc_lowlevel_device with the candidates, one launch)
+and `plant` (lmpc_sim_step_device reading the logged torques), with the controller's share of the two; `wbc` holds the
+WBC loop's whole tick.  The trot's height / roll / pitch bands of both loops come from their warm-up runs.
 """
 from __future__ import annotations
 
@@ -74,6 +82,109 @@ def start_of(batch, seed):
     return tuple(stack.to_bytes(x) for x in (robots, states, outs))
 
 
+def bands(x):
+    """[K][B][36] states -> the trot's height / roll / pitch bands over every robot and tick."""
+    f = lambda t: float(t)
+    return dict(height=[f(x[:, :, 5].min()), f(x[:, :, 5].max())], roll=[f(x[:, :, 2].min()), f(x[:, :, 2].max())],
+                pitch=[f(x[:, :, 1].min()), f(x[:, :, 1].max())])
+
+
+def fallen_count(x):
+    return int(((x[:, :, 1].abs() > 0.5) | (x[:, :, 2].abs() > 0.5) | (x[:, :, 5] < 0.5 * x[0, :, 5])).any(dim=0).sum())
+
+
+def low_level_rows(args):
+    """--low-level: the joint-PD loop beside the WBC loop, alternating runs, and the low-level tick's two parts."""
+    import torch
+
+    from legged_mpc_control_amd import BatchedConvexQPSolver, est, lowlevel, rbd, rollout, sim, stack, synth
+
+    dev = torch.device("cuda:0")
+    T, W = args.ticks, WBC_PER_MPC
+    rows = []
+    for batch in [int(b) for b in args.batches.split(",")]:
+        p, cfg, model = synth.params(), rollout.cfg_go1(), rbd.model_go1()
+        sc = sim.cfg(dt=SIM_DT, ground_z=0.0)
+        ll_cfg = lowlevel.cfg_go1(model)
+        wbc = stack.StackLoop(model, p, H, batch, cfg, sc, W)
+        ll = stack.StackLoop(model, p, H, batch, cfg, sc, W, low_level=ll_cfg)
+        start = [torch.from_numpy(a).to(dev) for a in start_of(batch, 4000 + batch)]
+        bufs = [a.clone() for a in start]
+        wlog = wbc.run_device(*bufs, T, log=True)  # warm-up runs, and the records of what the loops do
+        xw = wlog["states"].view(torch.float64)
+        row = dict(batch=batch, H=H, mpc_ticks=T, wbc_per_mpc=W, dense_path=ll.solver.dense_path)
+        row["wbc"] = dict(nonzero_status=dict(qp=int((wlog["qp_status"] != 0).sum()), wbc=int((wlog["wbc_status"] != 0).sum()),
+                                              sim=int((wlog["sim_status"] != 0).sum())),
+                          fallen=fallen_count(xw), bands=bands(xw))
+        del wlog, xw
+        for d, s in zip(bufs, start):
+            d.copy_(s)
+        log = ll.run_device(*bufs, T, log=True)
+        torch.cuda.synchronize()
+        x = log["states"].view(torch.float64)
+        row["lowlevel"] = dict(nonzero_status=dict(qp=int((log["qp_status"] != 0).sum()),
+                                                   nonfinite_tau=int((log["ll_flags"] & lowlevel.TAU_NONFINITE != 0).sum()),
+                                                   sim=int((log["sim_status"] != 0).sum())),
+                               flag_words=sorted(int(v) for v in torch.unique(log["ll_flags"]).cpu()),
+                               fallen=fallen_count(x), bands=bands(x), kp=ll_cfg.kp[0][0], kd=ll_cfg.kd[0][0])
+
+        def whole(loop):
+            def run():
+                for d, s in zip(bufs, start):
+                    d.copy_(s)
+                loop.run_device(*bufs, T)
+            return run
+
+        ms_w = ms_l = float("inf")
+        for _ in range(args.repeats):  # alternating: a drift of the box hits both loops alike
+            ms_w = min(ms_w, timed(whole(wbc), 1))
+            ms_l = min(ms_l, timed(whole(ll), 1))
+        row["wbc"]["whole"] = dict(ms_per_mpc_tick=ms_w / T, robot_ticks_per_s=batch * T / (ms_w * 1e-3))
+        row["lowlevel"]["whole"] = dict(ms_per_mpc_tick=ms_l / T, robot_ticks_per_s=batch * T / (ms_l * 1e-3))
+        cmds = log["cmd"].contiguous()
+        grf = torch.empty((batch, H, 12), dtype=torch.float64, device=dev)
+        solver = BatchedConvexQPSolver(p, H, max_batch=0)
+
+        def solve_only():
+            for t in range(T):
+                solver.solve_commands_device(cmds[t], grf)
+
+        solve_only()
+        torch.cuda.synchronize()
+        ms_solve = timed(solve_only, args.repeats)
+        K = W * T
+        prev = [start[1]] + [log["states"][k] for k in range(K - 1)]
+        prev_out = [start[2]] + [log["out"][k] for k in range(K - 1)]
+        gait = log["robots"].view(torch.int32)[:, :, est.GAIT_OFFSET]  # [T][B], the robots' stride
+        d_ll = torch.empty((batch, lowlevel.OUT_BYTES), dtype=torch.uint8, device=dev)
+        d_cand = torch.empty((batch, 4), dtype=torch.int32, device=dev)
+        d_next, d_o = torch.empty_like(start[1]), torch.empty_like(start[2])
+
+        def controller():
+            for k in range(K):
+                lowlevel.lowlevel_device(ll_cfg, prev[k], log["target"][k // W], d_ll, gait[k // W], prev_out[k], d_cand)
+
+        def plant():
+            for k in range(K):
+                sim.step_device(model, sc, prev[k], lowlevel.tau_view(log["ll_out"][k]), log["candidates"][k], d_next,
+                                d_o, 1)
+
+        parts = {}
+        for name, fn in (("controller", controller), ("plant", plant)):
+            fn()
+            torch.cuda.synchronize()
+            parts[name] = 1e3 * timed(fn, args.repeats) / K
+        row["lowlevel"].update(solve_only=dict(ms_per_tick=ms_solve / T), controller_us_per_tick=parts["controller"],
+                               plant_us_per_tick=parts["plant"],
+                               controller_share_of_low_level_tick=parts["controller"] / (parts["controller"] + parts["plant"]),
+                               glue_us_per_mpc_tick=1e3 * (ms_l - ms_solve) / T - W * (parts["controller"] + parts["plant"]))
+        rows.append(row)
+        solver.close()
+        wbc.close()
+        ll.close()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ticks", type=int, default=50)
@@ -82,8 +193,18 @@ def main():
     ap.add_argument("--wbc-warm", action="store_true")
     ap.add_argument("--batches", default=",".join(str(b) for b in BATCHES))
     ap.add_argument("--whole-only", action="store_true")
+    ap.add_argument("--low-level", action="store_true")
     args = ap.parse_args()
     import torch
+
+    if args.low_level:
+        line = json.dumps(dict(bench="stack_low_level", device=torch.cuda.get_device_name(0), configs=low_level_rows(args)))
+        print(line)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        return
 
     from legged_mpc_control_amd import BatchedConvexQPSolver, rbd, rollout, sim, stack, synth
 

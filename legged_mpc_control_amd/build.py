@@ -160,6 +160,9 @@ TEST_VARIANTS = {
     # the dense polish with every round refactorised (no range-space updates): tests/test_gpu_kkt.py checks that the
     # product's updates reach the same iteration words and forces
     "noschur": (["LMPC_POLISH_SCHUR=0"], ("lmpc_dense.hip", "lmpc_lq.hip", "lmpc_fused.hip")),
+    # the range-space rounds' per-QP counters (rounds, entries, columns, largest size, longest run) and the check of
+    # leg_free against the bases: tests/test_gpu_schur_rounds.py shows with them that its batches reach the code
+    "schurdiag": (["LMPC_SCHUR_DIAG"], ("lmpc_dense.hip", "lmpc_lq.hip", "lmpc_fused.hip")),
     # the dense path's diagonal tiles by diag_inverse (T and W = L^-1 in tiles of their own, two MFMAs per pivot) in
     # place of diag_inverse_merged: tests/test_gpu_dense_diag.py checks that the merged tile leaves every bit of the
     # answers where it was

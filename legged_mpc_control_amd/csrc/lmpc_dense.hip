@@ -41,7 +41,7 @@ namespace lmpc {
 
 // Diagnostic build only (-DLMPC_STAMPS): per-phase cycle counters of QP 0..4095 (tools/dense_check.py).
 #ifdef LMPC_STAMPS
-constexpr int DSTAMP_N = 14;
+constexpr int DSTAMP_N = 15;
 __device__ unsigned long long lmpc_dense_stamps[4096][DSTAMP_N];
 #define DSTAMP_DECL unsigned long long _ds_acc[DSTAMP_N] = {}; unsigned long long _ds_t0 = __builtin_readcyclecounter();
 #define DSTAMP(i) do { const unsigned long long _t = __builtin_readcyclecounter(); _ds_acc[i] += _t - _ds_t0; _ds_t0 = _t; } while (0)
@@ -82,6 +82,23 @@ extern "C" int lmpc_debug_refine(double* out, int nqp) {
 extern "C" int lmpc_debug_refine_clear(void) {
     static double zeros[LMPC_KKT_DIAG_QPS * 4];
     return hipMemcpyToSymbol(HIP_SYMBOL(lmpc_refine_diag), zeros, sizeof(zeros)) == hipSuccess ? 0 : -1;
+}
+#endif
+
+#ifdef LMPC_SCHUR_DIAG
+// diagnostic build (tests/test_gpu_schur_rounds.py): per QP, the range-space polish rounds it took -- [rounds, entries
+// built, column entries, largest nsch, longest run of consecutive range-space rounds, leg-steps whose basis column
+// counts differ from leg_free's]
+constexpr int LMPC_SCHUR_DIAG_QPS = 4096;
+__device__ double lmpc_schur_diag[LMPC_SCHUR_DIAG_QPS][6];
+extern "C" int lmpc_debug_schur(double* out, int nqp) {
+    if (nqp > LMPC_SCHUR_DIAG_QPS) nqp = LMPC_SCHUR_DIAG_QPS;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(lmpc_schur_diag), (size_t)nqp * 6 * sizeof(double)) == hipSuccess
+               ? nqp : -1;
+}
+extern "C" int lmpc_debug_schur_clear(void) {
+    static double zeros[LMPC_SCHUR_DIAG_QPS * 6];
+    return hipMemcpyToSymbol(HIP_SYMBOL(lmpc_schur_diag), zeros, sizeof(zeros)) == hipSuccess ? 0 : -1;
 }
 #endif
 

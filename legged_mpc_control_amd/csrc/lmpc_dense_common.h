@@ -695,6 +695,21 @@ __device__ __forceinline__ double h_matvec(const DSmem& S, const ldouble* x, ldo
     return ys + (lr < 3 ? tmp[lane < 48 ? lane : 0] : 0.0);
 }
 
+// lane v's element of H e for a vector e supported on leg-step b (components e3): the three elements H[v][w] of b's
+// variables w, three loads and three FMAs instead of h_matvec's whole product.  Row tiles up to b's tile hold the
+// element itself (the diagonal tiles are stored in full), the row tiles below it the transposed element of tile
+// (tw, tv).  Padding / unused lanes get 0 (their rows are identity rows).
+__device__ __forceinline__ double h_col3(const DSmem& S, int b, const double (&e3)[3], int lane) {
+    const int tv = lane >> 4, vw = lane & 15;
+    const int tw = b / 5, sw = 3 * (b - 5 * tw);
+    const bool up = tv <= tw;
+    const ldouble* T = S.Ht + (up ? tix(tv, tw) : tix(tw, tv)) * DN_TILE;
+    double h = 0.0;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) h = fma(T[up ? toff(vw, sw + q) : toff(sw + q, vw)], e3[q], h);
+    return h;
+}
+
 // ---------------------------------------------------------------------------
 // Prologue: record -> LDS, stance leg-step map (lsm, fb), terrain frames, I_w^-1, G0 = B rows 6-11,
 // yaw cos/sin of every step, per-leg input Hessian blocks.  smask = ballot of stance leg-steps

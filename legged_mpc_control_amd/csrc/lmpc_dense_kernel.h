@@ -7,6 +7,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 
 #include "lmpc/lmpc.h"
 #include "lmpc_device.h"
@@ -33,10 +34,12 @@ namespace lmpc {
 // LMPC_SCHUR_KMAX entries at most.  Cost rule in half-units of one solve: 2 per entry, LMPC_SCHUR_SLOPE2 per diagonal
 // tile a refactorisation would keep, at most LMPC_SCHUR_LIM2 (config 2 0.1827 -> 0.1731 ms against accepting every
 // qualifying round; rows-only rounds and a further charge per column's matvec were tried and dropped: DESIGN.md,
-// "Experiments removed from the source").
+// "Experiments removed from the source").  Slope 4 / limit 10 priced a round with a full matvec per column and a
+// padded 6 x 6 K; with the columns from h_col3 and K at its own size 3 / 11 is the fastest of the grid in
+// profiles/schur/ (config 2 0.1468 -> 0.1397 ms, 0.1446 at 4 / 10; 2 / 12, 2 / 14, 3 / 14 and 0 / 12 are slower).
 constexpr int LMPC_SCHUR_KMAX = 6;
-constexpr int LMPC_SCHUR_SLOPE2 = 4;
-constexpr int LMPC_SCHUR_LIM2 = 10;
+constexpr int LMPC_SCHUR_SLOPE2 = 3;
+constexpr int LMPC_SCHUR_LIM2 = 11;
 // interior-point start: z = LMPC_DENSE_Z0 / s (complementarity LMPC_DENSE_Z0 per pair); 0.3 and 3 ran config 2 in
 // 0.212 / 0.201 ms against 0.174 (profiles/r05, ab_z0.log)
 constexpr double LMPC_DENSE_Z0 = 1.0;
@@ -74,24 +77,25 @@ __device__ __forceinline__ int wave_prefix3(int k, unsigned long long below) {
            4 * __popcll(__ballot(k & 4) & below);
 }
 
-// One leg-step of a range-space polish round (dense_body): faces act against the factorised round's bact (basis
-// Tb in LDS; Tn = leg_basis(act), nap its apex flag).  The kept faces cm = act & bact leave nc free directions,
+// One leg-step of a range-space polish round (dense_body): faces act (nap: an apex) against the factorised round's
+// bact.  The kept faces cm = act & bact leave nc free directions,
 // nb of them the factorised ones: kc = nc - nb new columns, kr rows (the added faces, each removing one free
 // direction, or at a new apex the nc rows u = 0).  ok = false: the round refactorises.
 struct SchurLeg {
     int kc, kr;
     bool ok;
 };
-__device__ __forceinline__ SchurLeg schur_leg(bool chg, int act, int bact, bool nap, const ldouble* Tb,
-                                              const double Tn[9], double mu, double fzmax) {
+// The counts come from the face words alone: leg_basis leaves no free direction at an apex and otherwise three less
+// one per active face (its T has exactly that many nonzero columns), so no basis is built to evaluate the cost rule --
+// a leg_basis (five IEEE 1/sqrt, ~3.5 k cycles of a lone wave) less in every polish round after the first.
+__device__ __forceinline__ int leg_free(int a) { return ((a & 3) == 3 || (a & 12) == 12) ? 0 : 3 - __popc(a & 31); }
+__device__ __forceinline__ SchurLeg schur_leg(bool chg, int act, int bact, bool nap) {
     SchurLeg r{0, 0, true};
     if (!chg) return r;
     const bool bap = (bact & 3) == 3 || (bact & 12) == 12;
     if (bap && nap) return r;  // the force stays zero
     const int cm = act & bact;
-    double Tc[9], uc[3];
-    (void)leg_basis(cm, mu, fzmax, Tc, uc);
-    const int nb = ncols3(Tb), nc = ncols3(Tc), nn = ncols3(Tn);
+    const int nb = leg_free(bact), nc = leg_free(cm), nn = leg_free(act);
     r.kc = nc - nb;
     r.kr = nap ? nc : __popc(act & ~bact);
     // the factorised particular solution must lie in the kept space: no f_max face at an apex on either side
@@ -200,57 +204,55 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
     }
 #if LMPC_POLISH_SCHUR
     // K s = cv of a range-space round (S.scr: entries U / uleg / utyp / Cb, W = M^-1 V in Wc; every lane alike):
-    // K = Cb - V'W, rows by their three entries, entries beyond nsch the identity; L D L' without pivoting (K is
-    // quasi-definite: columns +, rows -).  Returns true (bad) when a pivot leaves its sign: rank-deficient in rounding.
-    auto schur_ksolve = [&](const double (&cv)[LMPC_SCHUR_KMAX], double (&sv)[LMPC_SCHUR_KMAX], double& kmin) -> bool {
+    // K = Cb - V'W, rows by their three entries; L D L' without pivoting (K is quasi-definite: columns +, rows -),
+    // unrolled to the round's own size (sv beyond it: 0).  Returns true (bad) when a pivot leaves its sign:
+    // rank-deficient in rounding.
+    auto schur_ksolve_n = [&](auto nc, const double (&cv)[LMPC_SCHUR_KMAX], double (&sv)[LMPC_SCHUR_KMAX],
+                              double& kmin) -> bool {
         constexpr int KM = LMPC_SCHUR_KMAX;
+        constexpr int N = decltype(nc)::value;  // = nsch: K at its own size, no padding formed
         const ldouble* U = S.scr + 48;
         const ldouble* uleg = U + 4 * KM;
         const ldouble* utyp = uleg + KM;
         const ldouble* Cb = utyp + KM;
         const ldouble* Wc = S.scr + 128;
-        double Am[KM][KM], sg[KM];
-        int rb_[KM];
-        bool rw[KM];
+        double Am[N][N], sg[N];
+        int rb_[N];
+        bool rw[N];
 #pragma unroll
-        for (int i = 0; i < KM; ++i) {
-            const bool iv = i < nsch;
-            rw[i] = iv && utyp[iv ? i : 0] < 0.5;
-            rb_[i] = iv ? (int)uleg[i] : 0;
+        for (int i = 0; i < N; ++i) {
+            rw[i] = utyp[i] < 0.5;
+            rb_[i] = (int)uleg[i];
             sg[i] = rw[i] ? -1.0 : 1.0;
         }
 #pragma unroll
-        for (int i = 0; i < KM; ++i) {
-            const bool iv = i < nsch;
+        for (int i = 0; i < N; ++i) {
 #pragma unroll
             for (int j = 0; j <= i; ++j) {
-                const bool jv = j < nsch;
-                double v = (iv && jv) ? Cb[KM * i + j] : (i == j ? 1.0 : 0.0);
-                if (iv && jv) {
-                    if (rw[i]) {
+                double v = Cb[KM * i + j];
+                if (rw[i]) {
 #pragma unroll
-                        for (int q = 0; q < 3; ++q) v = fma(-U[4 * i + q], Wc[64 * j + vidx(rb_[i], q)], v);
-                    } else if (rw[j]) {
+                    for (int q = 0; q < 3; ++q) v = fma(-U[4 * i + q], Wc[64 * j + vidx(rb_[i], q)], v);
+                } else if (rw[j]) {
 #pragma unroll
-                        for (int q = 0; q < 3; ++q) v = fma(-U[4 * j + q], Wc[64 * i + vidx(rb_[j], q)], v);
-                    }
+                    for (int q = 0; q < 3; ++q) v = fma(-U[4 * j + q], Wc[64 * i + vidx(rb_[j], q)], v);
                 }
                 Am[i][j] = v;
             }
         }
         bool bad = false;
-        double dd[KM];
+        double dd[N];
 #pragma unroll
-        for (int c = 0; c < KM; ++c) {
+        for (int c = 0; c < N; ++c) {
             double d = Am[c][c];
 #pragma unroll
             for (int b = 0; b < c; ++b) d = fma(-Am[c][b], Am[c][b] * dd[b], d);
             bad |= !(sg[c] * d > 1e-14 * fabs(Am[c][c]));
-            if (c < nsch) kmin = fmin(kmin, fabs(d) / fabs(Am[c][c]));  // pivot over its diagonal: K's cancellation
+            kmin = fmin(kmin, fabs(d) / fabs(Am[c][c]));  // pivot over its diagonal: K's cancellation
             dd[c] = d;
             const double inv = rcp_nr(d != 0.0 ? d : 1.0);
 #pragma unroll
-            for (int r = c + 1; r < KM; ++r) {
+            for (int r = c + 1; r < N; ++r) {
                 double v = Am[r][c];
 #pragma unroll
                 for (int b = 0; b < c; ++b) v = fma(-Am[r][b], Am[c][b] * dd[b], v);
@@ -258,26 +260,43 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
             }
         }
 #pragma unroll
-        for (int r = 0; r < KM; ++r) {  // L z = c
+        for (int r = 0; r < KM; ++r) sv[r] = 0.0;
+#pragma unroll
+        for (int r = 0; r < N; ++r) {  // L z = c
             double v = cv[r];
 #pragma unroll
             for (int b = 0; b < r; ++b) v = fma(-Am[r][b], sv[b], v);
             sv[r] = v;
         }
 #pragma unroll
-        for (int r = 0; r < KM; ++r) sv[r] = sv[r] * rcp_nr(dd[r] != 0.0 ? dd[r] : 1.0);
+        for (int r = 0; r < N; ++r) sv[r] = sv[r] * rcp_nr(dd[r] != 0.0 ? dd[r] : 1.0);
 #pragma unroll
-        for (int r = KM - 1; r >= 0; --r) {  // L' s = D^-1 z
+        for (int r = N - 1; r >= 0; --r) {  // L' s = D^-1 z
             double v = sv[r];
 #pragma unroll
-            for (int b = r + 1; b < KM; ++b) v = fma(-Am[b][r], sv[b], v);
+            for (int b = r + 1; b < N; ++b) v = fma(-Am[b][r], sv[b], v);
             sv[r] = v;
         }
         return bad;
     };
+    // dispatch on the round's (wave-uniform) size: nsch = 1 is one reciprocal
+    auto schur_ksolve = [&](const double (&cv)[LMPC_SCHUR_KMAX], double (&sv)[LMPC_SCHUR_KMAX], double& kmin) -> bool {
+        static_assert(LMPC_SCHUR_KMAX == 6, "one instance per size");
+        switch (nsch) {
+            case 1: return schur_ksolve_n(std::integral_constant<int, 1>{}, cv, sv, kmin);
+            case 2: return schur_ksolve_n(std::integral_constant<int, 2>{}, cv, sv, kmin);
+            case 3: return schur_ksolve_n(std::integral_constant<int, 3>{}, cv, sv, kmin);
+            case 4: return schur_ksolve_n(std::integral_constant<int, 4>{}, cv, sv, kmin);
+            case 5: return schur_ksolve_n(std::integral_constant<int, 5>{}, cv, sv, kmin);
+            default: return schur_ksolve_n(std::integral_constant<int, 6>{}, cv, sv, kmin);
+        }
+    };
     // a settled active set failed the certificate right after a range-space round: the same faces once more as a
     // factorised round before the retry ladder (the update's rounding, not the faces, may be what failed)
     bool force_fact = false, refact_done = false;
+#ifdef LMPC_SCHUR_DIAG
+    int sd_rounds = 0, sd_ent = 0, sd_col = 0, sd_max = 0, sd_run = 0, sd_runmax = 0, sd_mis = 0;
+#endif
 #endif
     for (;;) {
         if (mode == PRED) {
@@ -326,6 +345,7 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
             DSTAMP(13);  // Newton-matrix blocks D and weights
         }
         double Tn[9], upn[3];  // this polish round's leg basis (leg_basis of act)
+        SchurLeg sl{0, 0, true};  // this leg-step's entries, were the round a range-space one
         if (mode == POLISH) {
             ++prounds;
             apex = false;
@@ -338,14 +358,14 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
                 // factorised basis's nb; the update adds kc = nc - nb of them as new columns (faces dropped) and kr
                 // rows (faces added, or at a new apex the nc rows u = 0), each row removing one free direction.
                 // Not at an apex with the f_max face (its particular solution is not in the kept space).
-                const SchurLeg sl = schur_leg(st && act != bact, act, bact, apex, S.blk + 9 * lane, T, mu, fzmax);
+                sl = schur_leg(st && act != bact, act, bact, apex);
                 const int k = sl.kc + sl.kr;
                 nsch = wave_count3(k);
                 ncol = wave_count3(sl.kc);
                 // against a refactorisation from the first changed tile kt on (cheaper the later kt)
                 const unsigned long long dif = __ballot(st && act != bact);
                 const int kt = dif ? (__ffsll((long long)dif) - 1) / 5 : 4;
-                schur = __all(sl.ok) && nsch + ncol <= LMPC_SCHUR_KMAX &&
+                schur = __all(sl.ok) && nsch > 0 && nsch + ncol <= LMPC_SCHUR_KMAX &&
                         2 * nsch + LMPC_SCHUR_SLOPE2 * kt <= LMPC_SCHUR_LIM2;
             }
             // a factorised round: tiles ahead of the first leg-step whose faces differ from the last factorised
@@ -572,6 +592,9 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
             solve_vec();
 #if LMPC_POLISH_SCHUR
             if (mode == POLISH) {  // this factorised round's solution and faces: the base of range-space rounds
+#ifdef LMPC_SCHUR_DIAG
+                sd_run = 0;
+#endif
                 S.lua[lane] = S.vec[lane];
                 bact = act;
                 have_base = true;
@@ -595,11 +618,28 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
             ldouble* Cb = utyp + KM;       // KM x KM
             ldouble* Wc = S.scr + 128;     // M^-1 v_e by variable, 64 doubles each
             ldouble* Vc = Wc + 64 * nsch;  // the columns' v_e by variable (nsch + ncol <= KM)
-            const SchurLeg sl = schur_leg(st && act != bact, act, bact, apex, S.blk + 9 * lane, Tn, mu, fzmax);
             const unsigned long long below = (1ull << lane) - 1ull;
             const int e0 = wave_prefix3(sl.kc + sl.kr, below), c0 = wave_prefix3(sl.kc, below);
             if (lane < KM * KM) Cb[lane] = 0.0;
             LMPC_SYNC();
+#ifdef LMPC_SCHUR_DIAG
+            {
+                ++sd_rounds;
+                sd_ent += nsch;
+                sd_col += ncol;
+                sd_max = max(sd_max, nsch);
+                sd_runmax = max(sd_runmax, ++sd_run);
+                // leg_free against the bases themselves: the factorised one (LDS), this round's, the kept faces'
+                bool mis = false;
+                if (st && act != bact) {
+                    double Tk[9], uk[3];
+                    (void)leg_basis(act & bact, mu, fzmax, Tk, uk);
+                    mis = ncols3(S.blk + 9 * lane) != leg_free(bact) || ncols3(Tn) != leg_free(act) ||
+                          ncols3(Tk) != leg_free(act & bact);
+                }
+                sd_mis += __popcll(__ballot(mis));
+            }
+#endif
             if (sl.kc + sl.kr) {
                 const ldouble* Tb = S.blk + 9 * lane;
                 const ldouble* ub = S.lup + 3 * lane;
@@ -692,21 +732,15 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
                 }
             }
             LMPC_SYNC();
-            // columns: v = T'H e_t (one matvec each), and the t't'H block of Cb
+            // columns: v = T'H e_t (H e_t from three columns of H, h_col3), and the t't'H block of Cb
             if (ncol) {
                 const int w16 = lane & 15, bl = 5 * (lane >> 4) + w16 / 3, al = w16 % 3;
                 const bool vl = w16 < 15 && bl < nls;
                 for (int e = 0; e < nsch; ++e) {  // wave-uniform
                     const double ty = utyp[e];
                     if (ty < 0.5) continue;
-                    const int be = (int)uleg[e];
-                    S.vec2[lane] = 0.0;
-                    LMPC_SYNC();
-                    if (lane < 3) S.vec2[vidx(be, lane)] = U[4 * e + lane];
-                    LMPC_SYNC();
-                    const double h = h_matvec(S, S.vec2, S.scr, lane);
-                    LMPC_SYNC();
-                    S.vec2[lane] = h;
+                    const double t3[3] = {U[4 * e], U[4 * e + 1], U[4 * e + 2]};
+                    S.vec2[lane] = h_col3(S, (int)uleg[e], t3, lane);  // H e_t: three columns of H
                     LMPC_SYNC();
                     double v = 0.0;
                     if (vl) {
@@ -797,6 +831,7 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
             S.vec[lane] = bad ? S.lua[lane] : yv;
             if (bad) have_base = false;
             LMPC_SYNC();
+            DSTAMP(14);  // range-space round
         }
 #endif
         DSTAMP(5);  // solve
@@ -1132,6 +1167,13 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
             }
         }
     }
+#if LMPC_POLISH_SCHUR && defined(LMPC_SCHUR_DIAG)
+    if (lane == 0 && qp < LMPC_SCHUR_DIAG_QPS) {
+        const int sd[6] = {sd_rounds, sd_ent, sd_col, sd_max, sd_runmax, sd_mis};
+#pragma unroll
+        for (int i = 0; i < 6; ++i) lmpc_schur_diag[qp][i] = (double)sd[i];
+    }
+#endif
     if (!done) {
         qstatus = LMPC_QP_MAX_ITER;
 #pragma unroll

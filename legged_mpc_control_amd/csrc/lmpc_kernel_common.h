@@ -174,6 +174,8 @@ __device__ __forceinline__ ActiveRows active_rows(int act) {
 
 // Null-space parametrisation of one leg-step for active set `act` (bit i = row ci):
 // f = up + T y, T columns orthonormal.  Returns true at the pyramid apex (f = 0).
+// (T has 3 - popcount(act) nonzero columns, none at an apex: lmpc_dense_kernel.h's leg_free counts on that, and the
+// LMPC_SCHUR_DIAG build checks it, tests/test_gpu_schur_rounds.py)
 __device__ __forceinline__ bool leg_basis(int act, double mu, double fzmax, double T[9], double up[3]) {
 #pragma unroll
     for (int i = 0; i < 9; ++i) T[i] = 0.0;

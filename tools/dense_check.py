@@ -70,12 +70,12 @@ def stamps():
     g, st, it = s.solve(rec, con)
     L = N.lib()
     L.lmpc_debug_dense_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    buf = np.zeros((1024, 14), dtype=np.uint64)
+    buf = np.zeros((1024, 15), dtype=np.uint64)
     n = L.lmpc_debug_dense_stamps(buf.ctypes.data, 1024)
     names = ["prologue", "condense", "ipm leg-step + rhs", "M tiles (ipm)", "factor (MFMA part)", "solve", "diag tiles",
              "M tiles (polish)", "predictor step", "corrector step", "polish verify", "polish set-up + rhs",
-             "ipm: wave_sum of s'z", "ipm: D blocks + weights"]
-    tot = buf[:n, :14].sum(1).astype(float)
+             "ipm: wave_sum of s'z", "ipm: D blocks + weights", "range-space round"]
+    tot = buf[:n, :15].sum(1).astype(float)
     print(f"dense config 2: mean cycles/QP {tot.mean():.0f} (ipm {np.mean(it & 0xffff):.2f} rounds {np.mean(it >> 16):.2f})")
     for i, nm in enumerate(names):
         v = buf[:n, i].astype(float).mean()
@@ -83,7 +83,7 @@ def stamps():
     print(f"  max cycles/QP {tot.max():.0f}, p99 {np.percentile(tot, 99):.0f}")
     for q in np.argsort(-tot)[:6]:
         print(f"    slow QP {q}: {tot[q]:.0f} cycles, ipm {it[q] & 0xffff} rounds {it[q] >> 16}, "
-              f"diag {buf[q, 6]:.0f} solve {buf[q, 5]:.0f}")
+              f"diag {buf[q, 6]:.0f} solve {buf[q, 5]:.0f} range-space {buf[q, 14]:.0f}")
     L.lmpc_debug_condense_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int]
     cb = np.zeros((1024, 5), dtype=np.uint64)
     n = L.lmpc_debug_condense_stamps(cb.ctypes.data, 1024)

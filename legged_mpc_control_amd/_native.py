@@ -107,6 +107,9 @@ LOWLEVEL_SYMBOLS = (
 )
 LOWLEVEL_ABI_VERSION = 1
 LL_IK_NAN, LL_VEL_NAN, LL_TAU_NONFINITE, LL_CLAMPED = 1, 2, 4, 8
+# include/lmpc/lmpc_lowsim.h: the low-level ticks of an MPC tick (controller + plant) as one launch
+LOWSIM_SYMBOLS = ("lmpc_lowsim_abi_version", "lmpc_lowsim_block_robots", "lmpc_lowsim_run", "lmpc_lowsim_run_device")
+LOWSIM_ABI_VERSION = 1
 
 
 class LmpcParams(ctypes.Structure):
@@ -355,6 +358,12 @@ class LmpcLowlevelOut(ctypes.Structure):
         ("tau", ctypes.c_double * 12), ("joint_tau_tgt", ctypes.c_double * 12), ("joint_ang_tgt", ctypes.c_double * 12),
         ("joint_vel_tgt", ctypes.c_double * 12), ("flags", ctypes.c_int32 * 4),
     ]
+
+
+class LmpcLowsimLog(ctypes.Structure):
+    """lmpc_lowsim_log: host pointers for lmpc_lowsim_run, device pointers for lmpc_lowsim_run_device; each may be None."""
+    _fields_ = [("states", ctypes.c_void_p), ("outs", ctypes.c_void_p), ("ll_outs", ctypes.c_void_p),
+                ("candidates", ctypes.c_void_p)]
 
 
 class NativeLibraryError(RuntimeError):
@@ -668,6 +677,18 @@ def lib():
         if L.lmpc_lowlevel_abi_version() != LOWLEVEL_ABI_VERSION or ll_sizes != ll_mirrors:
             raise NativeLibraryError(f"{path}: lmpc_lowlevel.h ABI {L.lmpc_lowlevel_abi_version()} with struct sizes "
                                      f"{ll_sizes}, this binding is ABI {LOWLEVEL_ABI_VERSION} with {ll_mirrors}")
+        lgp = ctypes.POINTER(LmpcLowsimLog)
+        L.lmpc_lowsim_abi_version.restype = ctypes.c_int
+        L.lmpc_lowsim_block_robots.restype = ctypes.c_int
+        L.lmpc_lowsim_run.argtypes = [mp, ctypes.POINTER(LmpcSimCfg), lcp, sp, tp, i32p, ctypes.POINTER(LmpcSimOut), i32p, lop,
+                                      ctypes.c_int, ctypes.c_int, lgp]
+        L.lmpc_lowsim_run.restype = ctypes.c_int
+        L.lmpc_lowsim_run_device.argtypes = [mp, ctypes.POINTER(LmpcSimCfg), lcp, vp, vp, vp, ctypes.c_int64, vp, vp, vp,
+                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, lgp, vp]
+        L.lmpc_lowsim_run_device.restype = ctypes.c_int
+        if L.lmpc_lowsim_abi_version() != LOWSIM_ABI_VERSION:
+            raise NativeLibraryError(f"{path}: lmpc_lowsim.h ABI {L.lmpc_lowsim_abi_version()}, this binding is ABI "
+                                     f"{LOWSIM_ABI_VERSION}")
         if L.lmpc_rollout_abi_version() != ROLLOUT_ABI_VERSION or L.lmpc_robot_size() != ROBOT_BYTES:
             raise NativeLibraryError(f"{path}: lmpc_rollout.h ABI {L.lmpc_rollout_abi_version()} / lmpc_robot of "
                                      f"{L.lmpc_robot_size()} B, this binding is ABI {ROLLOUT_ABI_VERSION} / {ROBOT_BYTES} B")

@@ -43,12 +43,17 @@ SCHED_FLAGS = {
     "lmpc_fused.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"] + KERNEL_FP,
     "lmpc_gi.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],
     "lmpc_hoqp.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],
+    # the fused controller + plant kernel: no FP flag, as lmpc_sim.hip and lmpc_lowlevel.hip (its results are theirs bit
+    # for bit).  Without machine LICM the constants of the controller's sin / cos / atan2 / acos polynomials and the
+    # stores' addresses are not hoisted out of the tick loop, where they stayed live through the plant step, which has
+    # no register to spare: 66 VGPRs spilled (268 bytes of scratch) -> none (profiles/lowsim/registers.txt)
+    "lmpc_lowsim.hip": ["-mllvm", "-disable-machine-licm"],
 }
 
-SOURCES = ["lmpc_kernels.hip", "lmpc_lq.hip", "lmpc_fused.hip", "lmpc_dense.hip", "lmpc_gi.hip", "lmpc_prep.hip", "lmpc_rollout.hip", "lmpc_hoqp.hip", "lmpc_wbc.hip", "lmpc_rbd.hip", "lmpc_sim.hip", "lmpc_contact.hip", "lmpc_stack.hip", "lmpc_est.hip", "lmpc_lowlevel.hip", "lmpc_capi.cpp",
+SOURCES = ["lmpc_kernels.hip", "lmpc_lq.hip", "lmpc_fused.hip", "lmpc_dense.hip", "lmpc_gi.hip", "lmpc_prep.hip", "lmpc_rollout.hip", "lmpc_hoqp.hip", "lmpc_wbc.hip", "lmpc_rbd.hip", "lmpc_sim.hip", "lmpc_contact.hip", "lmpc_stack.hip", "lmpc_est.hip", "lmpc_lowlevel.hip", "lmpc_lowsim.hip", "lmpc_capi.cpp",
            "hoqp_capi.cpp", "lmpc_host.cpp", "ConvexQPSolver.cpp"]
 HEADERS = ["lmpc_device.h", "lmpc_common.h", "lmpc_kernel_common.h", "lmpc_dense_common.h", "lmpc_dense_kernel.h", "lmpc_lq_kernel.h",
-           "lmpc_hoqp_device.h", "lmpc_rbd_common.h", "lmpc_sim_common.h", "lmpc_contact_common.h", "lmpc_quad_device.h", "lmpc_stack_common.h", "lmpc_est_common.h", "lmpc_lowlevel_common.h"]
+           "lmpc_hoqp_device.h", "lmpc_rbd_common.h", "lmpc_sim_common.h", "lmpc_contact_common.h", "lmpc_quad_device.h", "lmpc_sim_device.h", "lmpc_stack_common.h", "lmpc_est_common.h", "lmpc_lowlevel_common.h", "lmpc_lowsim_common.h"]
 
 
 def hipcc() -> str:
@@ -65,6 +70,14 @@ def _stale(target: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def _compile_cmd(source: str, output, defines=(), flags=()) -> list:
+    """The compile line of one of SOURCES: the product's flags (HIP_FLAGS + that file's SCHED_FLAGS) + `flags`,
+    -D`defines`; `output`: what says what to produce (["-c", "-o", obj])."""
+    return [hipcc(), f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result",
+            "-I", os.path.join(ROOT, "include"), "-I", CSRC] + list(output) + HIP_FLAGS + \
+        SCHED_FLAGS.get(source, []) + list(flags) + [f"-D{d}" for d in defines] + [os.path.join(CSRC, source)]
+
+
 def _compile_lib(out: str, objdir: str, defines=(), flags=(), verbose: bool = False, only=None) -> str:
     """liblmpc from SOURCES: one compile per source (HIP_FLAGS + that file's SCHED_FLAGS + `flags`, -D`defines`),
     run in parallel, then one link; written to `out` atomically.  `only`: compile just these sources and link the
@@ -77,9 +90,7 @@ def _compile_lib(out: str, objdir: str, defines=(), flags=(), verbose: bool = Fa
             objs.append(os.path.join(LIBDIR, "obj", s + ".o"))
             continue
         obj = os.path.join(objdir, s + ".o")
-        cmd = [hipcc(), f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result",
-               "-I", os.path.join(ROOT, "include"), "-I", CSRC, "-c", "-o", obj] + HIP_FLAGS + \
-            SCHED_FLAGS.get(s, []) + list(flags) + [f"-D{d}" for d in defines] + [os.path.join(CSRC, s)]
+        cmd = _compile_cmd(s, ["-c", "-o", obj], defines, flags)
         if verbose:
             print(" ".join(cmd))
         procs.append((cmd, subprocess.Popen(cmd)))
@@ -93,6 +104,36 @@ def _compile_lib(out: str, objdir: str, defines=(), flags=(), verbose: bool = Fa
     return out
 
 
+def device_metadata(source: str) -> dict:
+    """{kernel name: {vgpr_count, sgpr_count, private_segment_fixed_size, vgpr_spill_count, sgpr_spill_count}} of one of
+    SOURCES, compiled for the device alone with the product's compile line (_compile_cmd) and read from the code object's
+    metadata in the assembly.  For tests that hold a kernel to "no scratch": a compiler upgrade can bring spills back without changing
+    a result."""
+    import re
+
+    asm = os.path.join(LIBDIR, "build", source + ".s")  # kept: compiled again only when a source or header is newer
+    deps = [os.path.join(CSRC, source), os.path.abspath(__file__)] + [os.path.join(CSRC, h) for h in HEADERS] + \
+        [os.path.join(ROOT, "include", "lmpc", h) for h in os.listdir(os.path.join(ROOT, "include", "lmpc"))]
+    if _stale(asm, deps):
+        os.makedirs(os.path.dirname(asm), exist_ok=True)
+        subprocess.run(_compile_cmd(source, ["--cuda-device-only", "-S", "-o", asm + ".tmp"],
+                                    flags=["-Wno-unused-command-line-argument"]), check=True)
+        os.replace(asm + ".tmp", asm)
+    text = open(asm).read()
+    out, cur = {}, {}
+    for line in text.splitlines():
+        m = re.match(r"\s+\.(name|vgpr_count|sgpr_count|private_segment_fixed_size|vgpr_spill_count|sgpr_spill_count):\s+(\S+)$",
+                     line)
+        if m and m.group(1) == "name":
+            cur["name"] = m.group(2)
+        elif m:
+            cur[m.group(1)] = int(m.group(2))
+        if line.strip().startswith(".wavefront_size") and "name" in cur:
+            out[cur.pop("name")] = cur
+            cur = {}
+    return out
+
+
 def build_native(force: bool = False, verbose: bool = False) -> str:
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     deps = srcs + [os.path.join(CSRC, h) for h in HEADERS] + [
@@ -100,7 +141,7 @@ def build_native(force: bool = False, verbose: bool = False) -> str:
         os.path.join(ROOT, "include", "lmpc", "lmpc_rollout.h"), os.path.join(ROOT, "include", "lmpc", "lmpc_rbd.h"),
         os.path.join(ROOT, "include", "lmpc", "lmpc_sim.h"), os.path.join(ROOT, "include", "lmpc", "lmpc_stack.h"),
         os.path.join(ROOT, "include", "lmpc", "lmpc_est.h"), os.path.join(ROOT, "include", "lmpc", "lmpc_contact.h"),
-        os.path.join(ROOT, "include", "lmpc", "lmpc_lowlevel.h"),
+        os.path.join(ROOT, "include", "lmpc", "lmpc_lowlevel.h"), os.path.join(ROOT, "include", "lmpc", "lmpc_lowsim.h"),
         os.path.join(ROOT, "include", "lmpc", "ConvexQPSolver.hpp"),
         os.path.abspath(__file__)]
     if not force and not _stale(LIB, deps):
@@ -303,6 +344,24 @@ def build_cpp_lowlevel_check(force: bool = False) -> str:
     out = os.path.join(ROOT, "tests", "cpp", "build", "lowlevel_host_check")
     deps = [src] + [os.path.join(CSRC, h) for h in ("lmpc_lowlevel_common.h", "lmpc_common.h")] + \
         [os.path.join(ROOT, "include", "lmpc", h) for h in ("lmpc_lowlevel.h", "lmpc_sim.h", "lmpc_rbd.h", "lmpc.h")]
+    if not force and not _stale(out, deps):
+        return out
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    cmd = [host_cxx(), "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+           "-Wno-unknown-pragmas", "-I", os.path.join(ROOT, "include"), "-I", CSRC, "-o", out, src]
+    subprocess.run(cmd, check=True)
+    return out
+
+
+def build_cpp_lowsim_check(force: bool = False) -> str:
+    """Stand-alone program over csrc/lmpc_lowsim_common.h (tests/cpp/lowsim_host_check.cpp): lmpc_lowsim_run's host
+    function against the explicit loop of controller and plant steps, built by the host compiler with AddressSanitizer and UBSan: host code only, no HIP and no liblmpc.so."""
+    src = os.path.join(ROOT, "tests", "cpp", "lowsim_host_check.cpp")
+    out = os.path.join(ROOT, "tests", "cpp", "build", "lowsim_host_check")
+    deps = [src] + [os.path.join(CSRC, h) for h in ("lmpc_lowlevel_common.h", "lmpc_sim_common.h", "lmpc_rbd_common.h",
+                                                    "lmpc_common.h", "lmpc_lowsim_common.h")] + \
+        [os.path.join(ROOT, "include", "lmpc", h) for h in ("lmpc_lowsim.h", "lmpc_lowlevel.h", "lmpc_sim.h", "lmpc_rbd.h",
+                                                            "lmpc.h")]
     if not force and not _stale(out, deps):
         return out
     os.makedirs(os.path.dirname(out), exist_ok=True)

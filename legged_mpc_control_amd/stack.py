@@ -15,7 +15,9 @@
     frictional contact model, include/lmpc/lmpc_contact.h): every foot is in its mask on every step and the candidate
     launch is gone.  With `low_level=lowlevel.cfg_go1(model)` the low-level tick is the reference's joint-PD controller
     (`lmpc_lowlevel_device`, include/lmpc/lmpc_lowlevel.h) instead of the whole-body controller: one launch that also
-    writes the candidates, then the plant, which reads the torques from the controller's output block by stride.
+    writes the candidates, then the plant, which reads the torques from the controller's output block by stride.  With
+    `fused_low_level=True` on top of it the `wbc_per_mpc` controller + plant launches of an MPC tick are one launch
+    (`lowsim.run_device`, include/lmpc/lmpc_lowsim.h) that leaves the same bits.
 
 What is restated from the reference and what is this library's choice (zero latency, the candidate rule, `touch` as
 the contact flag, the standing mode's foot targets, what a failed stage leaves): include/lmpc/lmpc_stack.h.  The
@@ -31,6 +33,7 @@ from . import _native as N
 from . import contact as C
 from . import est as E
 from . import lowlevel as LL
+from . import lowsim as LS
 from . import sim as S
 from .hoqp import check_device_tensor
 from .rbd import STATE_BYTES, TARGET_BYTES, WbcPipeline, target as wbc_target
@@ -210,7 +213,7 @@ class StackLoop:
                  rollout_cfg: N.LmpcRolloutCfg, sim_cfg: N.LmpcSimCfg, wbc_per_mpc: int, substeps: int = 1,
                  template: N.LmpcWbcTarget = None, device: int = 0, estimator: N.LmpcEstCfg = None,
                  plant: N.LmpcContactCfg = None, plant_split: bool = False, wbc_warm: bool = False,
-                 low_level: N.LmpcLowlevelCfg = None):
+                 low_level: N.LmpcLowlevelCfg = None, fused_low_level: bool = False):
         """estimator: an `lmpc_est_cfg` (est.cfg(dt=...)) closes the loop on the Kalman filter's estimate instead of the
         plant's own state; its dt must be the low-level tick's, substeps * sim_cfg.dt.  None: the plant's state is the
         feedback, exactly as without this option.
@@ -226,8 +229,19 @@ class StackLoop:
 
         low_level: an `lmpc_lowlevel_cfg` (lowlevel.cfg_go1(model)) runs the reference's joint-PD controller in place
         of the whole-body controller: no `WbcPipeline` is allocated, the template's WBC constants are not read, and
-        `wbc_warm` cannot be combined with it.  None: the whole-body controller, exactly as without this option."""
+        `wbc_warm` cannot be combined with it.  None: the whole-body controller, exactly as without this option.
+
+        fused_low_level: with `low_level`, the `wbc_per_mpc` low-level ticks of an MPC tick run as one launch
+        (`lowsim.run_device`) with the state in registers between them; buffers and logs end bit for bit as without it.
+        The estimator and the contact plant sit between the ticks and are not fused: it cannot be combined with
+        `estimator` or `plant`.  False: the present loop, launch for launch."""
         import torch
+
+        if fused_low_level and low_level is None:
+            raise ValueError("fused_low_level fuses the joint-PD controller with the plant: it needs low_level")
+        if fused_low_level and (estimator is not None or plant is not None):
+            raise ValueError("fused_low_level: the estimator and the contact plant run between the low-level ticks and are "
+                             "not fused")
 
         if low_level is not None and wbc_warm:
             raise ValueError("wbc_warm warm-starts the whole-body controller, which low_level replaces")
@@ -250,7 +264,7 @@ class StackLoop:
         dev = torch.device("cuda", device)
         self.solver = BatchedConvexQPSolver(params, self.H, max_batch=0, device=device)
         N.check(N.lib().lmpc_stack_reserve(self.solver._ctx, self.max_batch), "lmpc_stack_reserve")
-        self.low_level = low_level
+        self.low_level, self.fused_low_level = low_level, bool(fused_low_level)
         self.pipeline = WbcPipeline(model, self.max_batch, device, warm=wbc_warm) if low_level is None else None
         if low_level is not None:
             self.d_ll_out = torch.zeros((self.max_batch, LL.OUT_BYTES), dtype=torch.uint8, device=dev)
@@ -384,6 +398,16 @@ class StackLoop:
                     logs["qp_status"][t].copy_(d_qst)
                     logs["qp_iters"][t].copy_(d_qit)
                     logs["target"][t].copy_(d_target)
+                if self.fused_low_level:  # the W controller + plant ticks: one launch, logging its own rows
+                    rows = None
+                    if log:
+                        rows = {k: logs[k][t * W:(t + 1) * W] for k in ("states", "out", "ll_out", "candidates")}
+                    LS.run_device(self.model, self.sim_cfg, ll, d_state, d_target, d_sim_out, d_cand, d_ll, W, self.substeps,
+                                  d_gait, rows, s)
+                    if log:
+                        logs["tau"][t * W:(t + 1) * W].copy_(LL.tau_view(rows["ll_out"].view(W * B, LL.OUT_BYTES))
+                                                             .view(W, B, 12))
+                    continue
                 for i in range(W):
                     if ll is not None:  # the controller and, for this plant, its candidates: one launch
                         LL.lowlevel_device(ll, d_fb_state, d_target, d_ll, d_gait, d_sim_out if plant is None else None,

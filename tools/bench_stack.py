@@ -2,7 +2,7 @@
 """Benchmark of the full loop (include/lmpc/lmpc_stack.h: MPC -> WBC -> rigid-body plant) on MI355X.
 
     python tools/bench_stack.py [--ticks T] [--repeats R] [--out FILE] [--wbc-warm] [--batches 1024,4096] [--whole-only]
-                                [--low-level]
+                                [--low-level [--fused]]
 
 1024 and 4096 Go1 trot robots from a standing pose with seeded commands, H = 10, the reference's rates (10 ms MPC tick,
 8 low-level ticks of 1.25 ms).  One HIP event pair around a whole `StackLoop.run_device` of T MPC ticks, after a
@@ -28,6 +28,14 @@ best of R each).  The row's `lowlevel` holds the whole MPC tick, solve_only as a
 replayed on the loop's own logged data in two parts: `controller` (lmpc_lowlevel_device with the candidates, one launch)
 and `plant` (lmpc_sim_step_device reading the logged torques), with the controller's share of the two; `wbc` holds the
 WBC loop's whole tick.  The trot's height / roll / pitch bands of both loops come from their warm-up runs.
+
+--low-level --fused: `StackLoop(..., low_level=..., fused_low_level=True)` (include/lmpc/lmpc_lowsim.h: the 8 low-level
+ticks of an MPC tick as one launch) beside the unfused joint-PD loop of the same build from the same start, in
+ALTERNATING timed runs (unfused, fused, unfused, ...; R each).  The row holds both loops' best whole MPC tick, every
+single run (`runs_ms_per_mpc_tick`: the unfused runs' spread is the noise the gain is held against), whether the two
+loops' final buffers are bytewise equal, and the low-level ticks alone replayed on the unfused loop's logged data:
+`fused_launch_us_per_mpc_tick` (lmpc_lowsim_run_device, one launch per MPC tick) against `unfused_launches_us_per_mpc_tick`
+(its 8 controller + 8 plant launches).
 """
 from __future__ import annotations
 
@@ -185,6 +193,92 @@ def low_level_rows(args):
     return rows
 
 
+def fused_rows(args):
+    """--low-level --fused: the fused joint-PD loop beside the unfused one, alternating runs, and the low-level ticks of
+    an MPC tick alone in both forms."""
+    import torch
+
+    from legged_mpc_control_amd import est, lowlevel, lowsim, rbd, rollout, sim, stack, synth
+
+    dev = torch.device("cuda:0")
+    T, W = args.ticks, WBC_PER_MPC
+    rows = []
+    for batch in [int(b) for b in args.batches.split(",")]:
+        p, cfg, model = synth.params(), rollout.cfg_go1(), rbd.model_go1()
+        sc = sim.cfg(dt=SIM_DT, ground_z=0.0)
+        ll_cfg = lowlevel.cfg_go1(model)
+        loops = dict(unfused=stack.StackLoop(model, p, H, batch, cfg, sc, W, low_level=ll_cfg),
+                     fused=stack.StackLoop(model, p, H, batch, cfg, sc, W, low_level=ll_cfg, fused_low_level=True))
+        start = [torch.from_numpy(a).to(dev) for a in start_of(batch, 4000 + batch)]
+        bufs = [a.clone() for a in start]
+        finals, log = {}, None
+        for name, loop in loops.items():  # warm-up runs; the unfused one's log feeds the replays
+            for d, s in zip(bufs, start):
+                d.copy_(s)
+            lg = loop.run_device(*bufs, T, log=True)
+            torch.cuda.synchronize()
+            finals[name] = [b.clone() for b in bufs] + [lg["states"], lg["out"], lg["ll_out"], lg["candidates"]]
+            log = lg if name == "unfused" else log
+        row = dict(batch=batch, H=H, mpc_ticks=T, wbc_per_mpc=W, dense_path=loops["fused"].solver.dense_path,
+                   bytewise_equal=all(torch.equal(a, b) for a, b in zip(finals["unfused"], finals["fused"])),
+                   fallen=fallen_count(log["states"].view(torch.float64)))
+        finals.clear()
+
+        def whole(loop):
+            def run():
+                for d, s in zip(bufs, start):
+                    d.copy_(s)
+                loop.run_device(*bufs, T)
+            return run
+
+        runs = dict(unfused=[], fused=[])
+        for _ in range(args.repeats):  # alternating: a drift of the box hits both loops alike
+            for name, loop in loops.items():
+                runs[name].append(timed(whole(loop), 1) / T)
+        for name in loops:
+            best = min(runs[name])
+            row[name] = dict(ms_per_mpc_tick=best, robot_ticks_per_s=batch / (best * 1e-3), runs_ms_per_mpc_tick=runs[name])
+        row["unfused_spread_ms"] = max(runs["unfused"]) - min(runs["unfused"])
+        row["gain_ms_per_mpc_tick"] = row["unfused"]["ms_per_mpc_tick"] - row["fused"]["ms_per_mpc_tick"]
+        row["fused_is_faster_beyond_spread"] = row["gain_ms_per_mpc_tick"] > row["unfused_spread_ms"]
+        # the low-level ticks of every MPC tick alone, from the state the unfused loop had before them
+        before = [start[1]] + [log["states"][t * W - 1] for t in range(1, T)]
+        before_out = [start[2]] + [log["out"][t * W - 1] for t in range(1, T)]
+        gait = log["robots"].view(torch.int32)[:, :, est.GAIT_OFFSET]  # [T][B], the robots' stride
+        d_st, d_o = torch.empty_like(start[1]), torch.empty_like(start[2])
+        d_ll = torch.empty((batch, lowlevel.OUT_BYTES), dtype=torch.uint8, device=dev)
+        d_cand = torch.empty((batch, 4), dtype=torch.int32, device=dev)
+        tau = lowlevel.tau_view(d_ll)
+
+        def fused():
+            for t in range(T):
+                d_st.copy_(before[t]), d_o.copy_(before_out[t])
+                lowsim.run_device(model, sc, ll_cfg, d_st, log["target"][t], d_o, d_cand, d_ll, W, 1, gait[t])
+
+        def unfused():
+            for t in range(T):
+                d_st.copy_(before[t]), d_o.copy_(before_out[t])
+                for _ in range(W):
+                    lowlevel.lowlevel_device(ll_cfg, d_st, log["target"][t], d_ll, gait[t], d_o, d_cand)
+                    sim.step_device(model, sc, d_st, tau, d_cand, d_st, d_o, 1)
+
+        def copies():
+            for t in range(T):
+                d_st.copy_(before[t]), d_o.copy_(before_out[t])
+
+        parts = {}
+        for name, fn in (("copies", copies), ("fused", fused), ("unfused", unfused)):
+            fn()
+            torch.cuda.synchronize()
+            parts[name] = 1e3 * timed(fn, args.repeats) / T
+        row.update(fused_launch_us_per_mpc_tick=parts["fused"] - parts["copies"],
+                   unfused_launches_us_per_mpc_tick=parts["unfused"] - parts["copies"])
+        rows.append(row)
+        for loop in loops.values():
+            loop.close()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ticks", type=int, default=50)
@@ -194,11 +288,16 @@ def main():
     ap.add_argument("--batches", default=",".join(str(b) for b in BATCHES))
     ap.add_argument("--whole-only", action="store_true")
     ap.add_argument("--low-level", action="store_true")
+    ap.add_argument("--fused", action="store_true")
     args = ap.parse_args()
+    if args.fused and not args.low_level:
+        ap.error("--fused needs --low-level")
     import torch
 
     if args.low_level:
-        line = json.dumps(dict(bench="stack_low_level", device=torch.cuda.get_device_name(0), configs=low_level_rows(args)))
+        line = json.dumps(dict(bench="stack_low_level_fused" if args.fused else "stack_low_level",
+                               device=torch.cuda.get_device_name(0),
+                               configs=fused_rows(args) if args.fused else low_level_rows(args)))
         print(line)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -11,9 +11,14 @@ models below are derived from the Go1 fixture by seeded code, in the fixtures' J
     inertias on all 13 bodies, gravity 9.7;
   * feet     -- only foot[l] differs per leg, x and y non-zero;
   * bodies   -- only the legs' masses, centres of mass and inertias differ;
-  * origins  -- only joint_origin differs per leg, all three components non-zero.
+  * origins  -- only joint_origin differs per leg, all three components non-zero;
+  * limbs    -- for the joint-PD controller, whose kinematics cannot be read off the four above (they leave
+    A1Kinematics' class): the five lengths lmpc_leg_kin_from_model reads differ on every leg, thigh and calf differ,
+    every other component stays exactly 0, the bodies vary as in `bodies`, gravity 9.7.  It is not in NAMES: the
+    kernels' tests above do not need a fifth robot.
 
-The settings are plain dicts: the estimator's noises all different (a swap of two cannot cancel), its gravity, drift
+The joint-PD controller's settings (LL_GAINS, LL_LIMITS, LL_RHO_OPT, ll_cfg) have no two numbers alike, and LL_DEFECTS
+are the mistakes they tell apart (tests/test_lowlevel_models_host.py).  The other settings are plain dicts: the estimator's noises all different (a swap of two cannot cancel), its gravity, drift
 rule and init_P off default; the contact model around ground_z = 0.37 with and without recover_speed; the plant's
 ground off zero; WBC targets whose torque limits, mu and swing gains differ from robot to robot.  DEFECTS are the
 mistakes the sets exist to catch, written as changes to a model or to a configuration: tests/test_models_host.py shows
@@ -80,10 +85,8 @@ def _feet(seed=11):
     return _write(md, foot=foot)
 
 
-def _bodies(seed=12):
-    md = copy.deepcopy(model_json("go1"))
-    rng = np.random.default_rng(seed)
-    md["name"] = "bodies"
+def _vary_bodies(md, rng):
+    """The legs' masses, centres of mass and inertias, different from leg to leg (`bodies`' recipe, draw for draw)."""
     mass, com, inertia = np.array(md["mass"]), np.array(md["com"]), [list(x) for x in md["inertia"]]
     for l in range(4):
         mass[1 + 3 * l:4 + 3 * l] *= MASS_SCALE[l] * rng.uniform(0.9, 1.1, 3)
@@ -91,6 +94,13 @@ def _bodies(seed=12):
     for b in range(1, 13):
         inertia[b] = _box_inertia(rng, md["inertia"][b])
     return _write(md, mass=mass, com=com, inertia=inertia)
+
+
+def _bodies(seed=12):
+    md = copy.deepcopy(model_json("go1"))
+    rng = np.random.default_rng(seed)
+    md["name"] = "bodies"
+    return _vary_bodies(md, rng)
 
 
 def _origins(seed=13):
@@ -104,11 +114,36 @@ def _origins(seed=13):
     return _write(md, joint_origin=jo)
 
 
+# what lmpc_leg_kin_from_model reads of a leg, as (field, row within the leg, component), in rho_fix's order: ox, oy, d,
+# -lt, -lc; every other component of those four vectors must be zero for the model to lie in A1Kinematics' class
+LIMB_READS = (("joint_origin", 0, 0), ("joint_origin", 0, 1), ("joint_origin", 1, 1), ("joint_origin", 2, 2), ("foot", 0, 2))
+
+
+def _limbs(seed=14):
+    """Inside A1Kinematics' class (the controller's kinematics can be read off it) with no two legs alike: the five
+    lengths of every leg scaled on their own, thigh by ORIGIN_SCALE and calf by FOOT_SCALE; the zeros stay zeros and the
+    signs stay, so oy and d still tell left from right."""
+    md = copy.deepcopy(model_json("go1"))
+    rng = np.random.default_rng(seed)
+    md["name"], md["gravity"] = "limbs", 9.7
+    _vary_bodies(md, rng)
+    jo, foot = np.array(md["joint_origin"]), np.array(md["foot"])
+    for l in range(4):
+        f = rng.uniform(0.9, 1.1, 5)
+        for k, (field, row, comp) in enumerate(LIMB_READS):
+            if field == "foot":
+                foot[l, comp] *= FOOT_SCALE[l] * f[k]
+            else:
+                jo[3 * l + row, comp] *= ORIGIN_SCALE[l] * f[k]
+    return _write(md, joint_origin=jo, foot=foot)
+
+
 @functools.lru_cache(maxsize=None)
 def _models():
     out = {"lopsided": _lopsided(), "feet": _feet(), "bodies": _bodies(), "origins": _origins()}
     for name, md in out.items():
         check(md, VARIES[name])
+    out["limbs"] = check_limbs(_limbs())
     return out
 
 
@@ -149,6 +184,35 @@ def check(md, varies):
             assert np.all(np.asarray(md[field]) != 0.0), field
     if "inertia" in varies:
         assert np.all(np.asarray(md["inertia"])[1:] != 0.0)
+    return md
+
+
+def check_limbs(md):
+    """`check` for the bodies; the geometry: lmpc_leg_kin_from_model accepts it, every component it does not read is
+    exactly 0, the left / right signs are Go1's, no two legs share the magnitude of any of the five rho_fix numbers, and
+    thigh and calf differ on every leg."""
+    import ctypes
+
+    from legged_mpc_control_amd import _native as N
+    from legged_mpc_control_amd import rbd
+
+    go1 = model_json("go1")
+    check(dict(md, joint_origin=go1["joint_origin"], foot=go1["foot"]), ("mass", "com", "inertia"))
+    read = {"joint_origin": np.zeros((12, 3), dtype=bool), "foot": np.zeros((4, 3), dtype=bool)}
+    for l in range(4):
+        for field, row, comp in LIMB_READS:
+            read[field][(3 * l + row) if field == "joint_origin" else l, comp] = True
+    for field, mask in read.items():
+        a = np.asarray(md[field])
+        assert np.all(a[~mask] == 0.0) and np.all(a[mask] != 0.0), field
+        assert np.array_equal(np.sign(a), np.sign(np.asarray(go1[field]))), field
+    kin = N.LmpcLegKin()
+    assert N.lib().lmpc_leg_kin_from_model(ctypes.byref(rbd.model_from_json(md)), ctypes.byref(kin)) == 0
+    rf = np.array([list(r) for r in kin.rho_fix])
+    for k in range(5):
+        assert len(set(np.abs(rf[:, k]))) == 4, f"two legs share |rho_fix[.][{k}]|"
+    assert np.all(rf[:, 3] != rf[:, 4]) and np.all(rf[:, 3:] > 0.0)
+    assert np.array_equal(rf[:, 1] > 0, [True, False, True, False]) and np.array_equal(np.sign(rf[:, 1]), np.sign(rf[:, 2]))
     return md
 
 
@@ -242,3 +306,117 @@ def defective(name, defect):
     md = model(name)
     MODEL_DEFECTS[defect][0](md)
     return md
+
+
+# ---- the joint-PD controller's settings ------------------------------------------------------------------------------
+# Every lmpc_lowlevel_cfg of the presets' tests holds one kp, one kd, one limit (or none), rho_opt = 0 and four rho_fix
+# rows that are one row up to signs.  Here no two numbers are alike.
+def _ll_gains(seed=31):
+    rng = np.random.default_rng(seed)
+    kp = rng.permutation(np.linspace(0.5, 15.0, 12)).reshape(4, 3)  # the reference's Go1 and A1 gain sets are the ends
+    kd = rng.permutation(np.linspace(0.2, 0.6, 12)).reshape(4, 3)
+    assert len(set(kp.reshape(-1))) == 12 and len(set(kd.reshape(-1))) == 12
+    assert not any(np.array_equal(a, b) for a in kp for b in kd)
+    assert not np.array_equal(kp, kp.reshape(3, 4).T)  # a joint-major read shows
+    return dict(kp=kp, kd=kd)
+
+
+def _ll_rho_opt(seed=32):
+    """Magnitudes in [0.005, 0.02], signs mixed; rho_opt[l][1] takes the sign of the leg's d = rho_fix[l][2] (positive on
+    the left): fk and the Jacobian use d + rho_opt[1], inv_kin uses d, and with the opposite sign targets made by fk fall
+    where inv_kin's L^2 = Zf^2 + Yf_^2 - d^2 is negative."""
+    rng = np.random.default_rng(seed)
+    ro = rng.uniform(0.005, 0.02, (4, 3)) * rng.choice([-1.0, 1.0], (4, 3))
+    ro[:, 1] = np.abs(ro[:, 1]) * [1.0, -1.0, 1.0, -1.0]
+    for k in (0, 2):
+        assert {-1.0, 1.0} == set(np.sign(ro[:, k])), "signs not mixed: choose another seed"
+    assert len(set(np.abs(ro).reshape(-1))) == 12
+    return ro
+
+
+LL_GAINS = _ll_gains()
+LL_LIMITS = (9.0, 14.0, 21.0)
+LL_RHO_OPT = _ll_rho_opt()
+LL_SKEW_SCALE = (0.9, 1.0, 1.1, 1.2)  # per leg, times a seeded factor per number
+LL_KINDS = ("skew", "skew_limited", "limbs")
+
+
+def ll_cfg(kind):
+    """An lmpc_lowlevel_cfg with LL_GAINS and
+      "skew"          Go1's kinematics (lmpc_leg_kin_from_model) with every one of the 20 rho_fix numbers rescaled on its
+                      own, so that no two match in magnitude, LL_RHO_OPT, no torque limit;
+      "skew_limited"  the same with LL_LIMITS;
+      "limbs"         the kinematics of the `limbs` model (rho_opt = 0) with LL_LIMITS."""
+    from legged_mpc_control_amd import lowlevel as LL
+    from legged_mpc_control_amd import rbd
+
+    assert kind in LL_KINDS, kind
+    if kind == "limbs":
+        return LL.cfg_go1(rbd.model_from_json(model("limbs")), kp=LL_GAINS["kp"], kd=LL_GAINS["kd"], tau_limit=LL_LIMITS)
+    c = LL.cfg_go1(rbd.model_go1(), kp=LL_GAINS["kp"], kd=LL_GAINS["kd"],
+                   tau_limit=LL_LIMITS if kind == "skew_limited" else None)
+    rng = np.random.default_rng(33)
+    rf = np.array([list(r) for r in c.kin.rho_fix]) * np.array(LL_SKEW_SCALE)[:, None] * rng.uniform(0.95, 1.05, (4, 5))
+    assert len(set(np.abs(rf).reshape(-1))) == 20
+    for l in range(4):
+        c.kin.rho_fix[l][:] = [float(v) for v in rf[l]]
+        c.kin.rho_opt[l][:] = [float(v) for v in LL_RHO_OPT[l]]
+    return c
+
+
+def _ll_rows(c, name):
+    obj = c.kin if name.startswith("rho") else c
+    return np.array([list(r) for r in getattr(obj, name)])
+
+
+def _ll_set(c, name, a):
+    obj = c.kin if name.startswith("rho") else c
+    for l in range(4):
+        getattr(obj, name)[l][:] = [float(v) for v in a[l]]
+
+
+def _kp_transposed(c):
+    """kp[l][k] read joint-major, as the reference's kp_foot(k, leg) lies in memory."""
+    _ll_set(c, "kp", _ll_rows(c, "kp").reshape(3, 4).T)
+
+
+def _gains_leg0(c):
+    for name in ("kp", "kd"):
+        _ll_set(c, name, np.tile(_ll_rows(c, name)[0], (4, 1)))
+
+
+def _kp_kd_exchanged(c):
+    kp, kd = _ll_rows(c, "kp"), _ll_rows(c, "kd")
+    _ll_set(c, "kp", kd), _ll_set(c, "kd", kp)
+
+
+def _limit0(c):
+    c.tau_limit[:] = [float(c.tau_limit[0])] * 3
+
+
+def _rho_opt_zero(c):
+    _ll_set(c, "rho_opt", np.zeros((4, 3)))
+
+
+def _rho_fix_leg0(c):
+    """Leg 0's lengths on every lane, each leg's own signs kept."""
+    rf = _ll_rows(c, "rho_fix")
+    _ll_set(c, "rho_fix", np.sign(rf) * np.abs(rf[0]))
+
+
+# name -> (change to an lmpc_lowlevel_cfg, the ll_cfg kind it targets, whether the presets' cfgs hide it).  The presets'
+# kp and kd differ from each other (0.5 / 0.3, 15 / 0.4), so a whole-table exchange shows there already; what they hide
+# is every mistake inside a table.
+LL_DEFECTS = {"kp transposed within its 12 doubles": (_kp_transposed, "skew", True),
+              "leg 0's kp and kd in every leg": (_gains_leg0, "skew", True),
+              "kp and kd exchanged": (_kp_kd_exchanged, "skew", False),
+              "tau_limit[0] for every joint": (_limit0, "skew_limited", True),
+              "rho_opt read as zero": (_rho_opt_zero, "skew", True),
+              "leg 0's rho_fix magnitudes in every leg": (_rho_fix_leg0, "limbs", True)}
+
+
+def ll_defective(c, defect):
+    """A copy of the cfg with the defect applied."""
+    bad = type(c).from_buffer_copy(bytes(c))
+    LL_DEFECTS[defect][0](bad)
+    return bad

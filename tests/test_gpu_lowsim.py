@@ -24,9 +24,7 @@ from legged_mpc_control_amd import lowsim as LS
 from test_gpu_lowlevel import TROT_SPECS, gains, make_loop, not_fallen, upload
 from test_gpu_sim import standing_cases
 from test_gpu_stack import lowered, to_host
-from test_lowlevel_host import cfg_for
-from test_lowsim_host import COUNTS, robots, sim_cfg
-from test_rbd_host import preset
+from test_lowsim_host import COUNTS, robots, setup_for
 
 pytestmark = pytest.mark.gpu
 
@@ -65,8 +63,9 @@ def inputs(torch, rbs, gait):
 
 def run_unfused(torch, name, rbs, ticks, substeps, gait="packed", start=None):
     """`ticks` x (lowlevel_device with the candidates, step_device in place) -> dict of NumPy arrays: the final state,
-    out, ll_out, candidates ([B][...]) and a snapshot of each after every tick (states_log ... [ticks][B][...])."""
-    model, c, sc = preset(name), cfg_for(name), sim_cfg()
+    out, ll_out, candidates ([B][...]) and a snapshot of each after every tick (states_log ... [ticks][B][...]).  name: a
+    preset's, or a (model, joint-PD cfg, plant cfg) triple."""
+    model, c, sc = setup_for(name) if isinstance(name, str) else name
     d_state, d_target, d_out, d_gait = inputs(torch, rbs, gait)
     if start is not None:
         d_state.copy_(torch.from_numpy(start[0]).cuda()), d_out.copy_(torch.from_numpy(start[1]).cuda())
@@ -89,7 +88,7 @@ def run_unfused(torch, name, rbs, ticks, substeps, gait="packed", start=None):
 def run_fused(torch, name, rbs, ticks, substeps, gait="packed", logs=tuple(WIDTHS), start=None):
     """lowsim.run_device, one launch, GUARD prefilled rows behind every buffer and log array (asserted untouched) -> the
     same dict as run_unfused (only the requested logs)."""
-    model, c, sc = preset(name), cfg_for(name), sim_cfg()
+    model, c, sc = setup_for(name) if isinstance(name, str) else name
     d_state0, d_target, d_out0, d_gait = inputs(torch, rbs, gait)
     if start is not None:
         d_state0.copy_(torch.from_numpy(start[0]).cuda()), d_out0.copy_(torch.from_numpy(start[1]).cuda())
@@ -224,12 +223,13 @@ def test_mixed_gait_words_and_strides(gpu):
 
 
 # ---- the loop ------------------------------------------------------------------------------------------------------
-def run_loop(gpu, fused, wbc_per_mpc, sim_dt, ticks, name="go1", specs=None, log=True):
-    """StackLoop on four Go1 trot robots -> a list of (log, finals) per entry of `ticks`, run one after the other."""
+def run_loop(gpu, fused, wbc_per_mpc, sim_dt, ticks, name="go1", specs=None, log=True, low_level=None):
+    """StackLoop on four Go1 trot robots -> a list of (log, finals) per entry of `ticks`, run one after the other.
+    low_level: the joint-PD cfg (default: gains(name))."""
     _, states, _ = standing_cases()
     specs = specs or [((0.0, 0.0), 0.0), ((0.3, 0.0), 0.0), ((0.2, -0.1), 0.2), ((-0.2, 0.0), -0.3)]
-    loop, rbs, sts, outs = make_loop(lowered(states), specs, wbc_per_mpc, sim_dt, N.GAIT_TROT, gains(name),
-                                     fused_low_level=fused)
+    loop, rbs, sts, outs = make_loop(lowered(states), specs, wbc_per_mpc, sim_dt, N.GAIT_TROT,
+                                     low_level or gains(name), fused_low_level=fused)
     assert loop.fused_low_level == fused
     bufs = upload(gpu, rbs, sts, outs)
     res = []

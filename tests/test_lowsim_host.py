@@ -10,6 +10,9 @@ crouch (joints near (0, 0.8, -1.6)) with the lowest foot 1 um below the ground, 
   2  stand: LMPC_GAIT_STAND (movement mode 0), the weight on four feet;
   3  trot with the other diagonal, perturbed joints and a sideways velocity.
 
+`make_robots` is that recipe over a model, a seed and a ground height (tests/test_lowlevel_models_host.py builds the
+`limbs` robot's sets with it); `explicit_loop` takes a preset's name or a (model, joint-PD cfg, plant cfg) triple.
+
 `test_input_conditions` asserts on the explicit loop's own logs (not on the new code) that these inputs reach what the
 fused kernel must get right: a candidate word that changes between two ticks, a foot released by the unilateral rule,
 and a touch-down (touch 0 -> 1) inside the run.
@@ -41,23 +44,28 @@ def sim_cfg():
     return sim.cfg(dt=SIM_DT, ground_z=0.0)
 
 
-@functools.lru_cache(maxsize=None)
-def robots(name):
-    """COUNTS[name] robots: dicts of kind, state (LmpcRbdState), target (LmpcWbcTarget), gait (the gait word) and out
-    (the lmpc_sim_out the first tick reads its candidates from: held = touch = the foot is on or below the ground)."""
-    model = preset(name)
-    rng = np.random.default_rng(SEED + (0 if name == "go1" else 1))
+CROUCH = (0.0, 0.8, -1.6) * 4
+
+
+def make_robots(model, count, seed, ground_z=0.0, lift=0.03, push=1.0, crouch=CROUCH):
+    """`count` robots of `model` by the recipe above, the ground at `ground_z`: dicts of kind, state (LmpcRbdState),
+    target (LmpcWbcTarget), gait (the gait word) and out (the lmpc_sim_out the first tick reads its candidates from:
+    held = touch = the foot is on or below the ground).  lift: how far up the swing feet are sent [m]; push: the stance
+    feet's forces_des as a multiple of the weight they carry; crouch: the 12 joint angles the robots stand near.  The
+    joint-PD cfg is not read: the targets are the plant's
+    own feet."""
+    rng = np.random.default_rng(seed)
     weight = sum(model.mass) * model.gravity
     out = []
-    for i in range(COUNTS[name]):
+    for i in range(count):
         kind = KINDS[i % 4]
         s = np.zeros(36)
         s[0] = rng.uniform(-np.pi, np.pi)
         s[1:3] = rng.uniform(-0.02, 0.02, 2)
         s[3:5] = rng.uniform(-1.0, 1.0, 2)
-        s[6:18] = np.tile([0.0, 0.8, -1.6], 4) + rng.uniform(-0.05, 0.05, 12) * (1.0 if kind == "trot2" else 0.2)
+        s[6:18] = np.array(crouch) + rng.uniform(-0.05, 0.05, 12) * (1.0 if kind == "trot2" else 0.2)
         feet = np.array(sim.forward_dynamics(model, rbd.state_from_vector(s), np.zeros(12), (0, 0, 0, 0), True).foot_pos)
-        s[5] = -feet[2::3].min() + (2e-4 if kind == "drop" else -1e-6)
+        s[5] = ground_z - feet[2::3].min() + (2e-4 if kind == "drop" else -1e-6)
         if kind == "drop":
             s[23] = -0.05
         if kind == "trot2":
@@ -67,9 +75,9 @@ def robots(name):
         forces, pos_des = np.zeros(12), feet.copy()
         for l in range(4):
             if l in swing:
-                pos_des[3 * l + 2] += 0.03
+                pos_des[3 * l + 2] += lift
             else:
-                forces[3 * l + 2] = weight / (4 - len(swing))
+                forces[3 * l + 2] = push * weight / (4 - len(swing))
         t = rbd.target()
         t.forces_des[:] = [float(v) for v in forces]
         t.foot_pos_des[:] = [float(v) for v in pos_des]
@@ -77,16 +85,28 @@ def robots(name):
         o = N.LmpcSimOut()
         o.foot_pos[:] = [float(v) for v in feet]
         for l in range(4):
-            o.held[l] = o.touch[l] = int(feet[3 * l + 2] <= 0.0)
+            o.held[l] = o.touch[l] = int(feet[3 * l + 2] <= ground_z)
         out.append(dict(kind=kind, state=rbd.state_from_vector(s), target=t, out=o,
                         gait=N.GAIT_STAND if kind == "stand" else N.GAIT_TROT))
     return out
 
 
+@functools.lru_cache(maxsize=None)
+def robots(name):
+    """COUNTS[name] robots of the preset `name` on the ground z = 0."""
+    return make_robots(preset(name), COUNTS[name], SEED + (0 if name == "go1" else 1))
+
+
+def setup_for(name):
+    """(model, joint-PD cfg, plant cfg) of a preset: what the loops below run a robot on."""
+    return preset(name), cfg_for(name), sim_cfg()
+
+
 def explicit_loop(name, rb, ticks, substeps):
     """The yardstick: per tick the candidates from the last lmpc_sim_out, lmpc_lowlevel, lmpc_sim_step `substeps` times.
+    name: a preset's, or a (model, joint-PD cfg, plant cfg) triple.
     -> dict of per-tick lists (states, outs, ll_outs as bytes; candidates as lists)."""
-    model, c, sc = preset(name), cfg_for(name), sim_cfg()
+    model, c, sc = setup_for(name) if isinstance(name, str) else name
     st, o = rb["state"], rb["out"]
     log = dict(states=[], outs=[], ll_outs=[], candidates=[])
     for _ in range(ticks):

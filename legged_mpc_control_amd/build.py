@@ -208,6 +208,11 @@ TEST_VARIANTS = {
     # place of diag_inverse_merged: tests/test_gpu_dense_diag.py checks that the merged tile leaves every bit of the
     # answers where it was
     "diag2tile": (["LMPC_DIAG_TWO_TILES"], ("lmpc_dense.hip", "lmpc_lq.hip", "lmpc_fused.hip")),
+    # the dense polish with leg_basis called where a round needs a basis, in place of the per-QP face-set table:
+    # tests/test_gpu_basis_table.py checks that the table leaves every bit of the answers where it was
+    "basisdirect": (["LMPC_BASIS_TABLE=0"], ("lmpc_dense.hip", "lmpc_lq.hip", "lmpc_fused.hip")),
+    # the product plus lmpc_debug_basis_probe: the table's builder and reader against leg_basis on all 32 face words
+    "basisprobe": (["LMPC_BASIS_PROBE"], ("lmpc_dense.hip",)),
 }
 
 

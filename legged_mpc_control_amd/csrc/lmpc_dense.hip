@@ -122,6 +122,55 @@ template __global__ void lmpc_dense_kernel<false>(const DevParams, const double*
 template __global__ void lmpc_dense_kernel<true>(const DevParams, const double*, const uint8_t*, const double*, int,
                                                  double*, int32_t*, int32_t*, uint8_t*);
 
+#ifdef LMPC_BASIS_PROBE
+// test build only (tests/test_gpu_basis_table.py): the kernel's own table builder and reader for (mu, f_max) and,
+// from a kernel of its own (so that the compiler cannot merge the two evaluations), leg_basis per face word.
+// Row a of either: [T(9) up(3) apex]
+__global__ void __launch_bounds__(64) lmpc_basis_probe_table_kernel(double mu, double fzmax, double* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) double sm[DN_BT];
+    const int lane = threadIdx.x;
+    ldouble* bt = (ldouble*)sm;
+    basis_table_build(bt, mu, fzmax, lane);
+    LMPC_SYNC();
+    if (lane < 32) {
+        double T[9], up[3];
+        const bool ap = basis_table_read(bt, lane, T, up);
+        double* o = out + 13 * lane;
+#pragma unroll
+        for (int e = 0; e < 9; ++e) o[e] = T[e];
+#pragma unroll
+        for (int p = 0; p < 3; ++p) o[9 + p] = up[p];
+        o[12] = ap ? 1.0 : 0.0;
+    }
+}
+__global__ void __launch_bounds__(64) lmpc_basis_probe_direct_kernel(double mu, double fzmax, double* __restrict__ out) {
+    const int lane = threadIdx.x;
+    if (lane < 32) {
+        double T[9], up[3];
+        const bool ap = leg_basis(lane, mu, fzmax, T, up);
+        double* o = out + 13 * lane;
+#pragma unroll
+        for (int e = 0; e < 9; ++e) o[e] = T[e];
+#pragma unroll
+        for (int p = 0; p < 3; ++p) o[9 + p] = up[p];
+        o[12] = ap ? 1.0 : 0.0;
+    }
+}
+// out (host): 2 x 32 x 13 doubles, the table's rows then leg_basis's
+extern "C" int lmpc_debug_basis_probe(double mu, double fzmax, double* out) {
+    double* d = nullptr;
+    const size_t bytes = 2 * 32 * 13 * sizeof(double);
+    if (hipMalloc((void**)&d, bytes) != hipSuccess) return -1;
+    hipLaunchKernelGGL(lmpc_basis_probe_table_kernel, dim3(1), dim3(LMPC_WAVE), 0, 0, mu, fzmax, d);
+    bool ok = hipGetLastError() == hipSuccess;
+    hipLaunchKernelGGL(lmpc_basis_probe_direct_kernel, dim3(1), dim3(LMPC_WAVE), 0, 0, mu, fzmax, d + 32 * 13);
+    ok = ok && hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+         hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+    (void)hipFree(d);
+    return ok ? 0 : -1;
+}
+#endif
+
 #ifdef LMPC_STAMPS
 extern "C" int lmpc_debug_condense_stamps(unsigned long long* out, int nqp) {
     if (nqp > 4096) nqp = 4096;
@@ -136,7 +185,7 @@ extern "C" int lmpc_debug_dense_stamps(unsigned long long* out, int nqp) {
 #endif
 
 size_t dense_lds_bytes(int H) {
-    const int doubles = 40 + 72 + 24 + 36 + 10 * DN_TILE + 64 * 3 + 180 + 60 + 64 + 2 * H + 12 * H + 64 + DN_SCR_MIN;
+    const int doubles = 40 + 72 + 24 + 36 + 10 * DN_TILE + 64 * 3 + 180 + 60 + 64 + 2 * H + 12 * H + 64 + DN_SCR_MIN + DN_BT;
     return (size_t)doubles * sizeof(double) + (20 + 33) * sizeof(int);
 }
 

@@ -139,9 +139,16 @@ struct DSmem {
     ldouble* scr;   // union: condensation: mu by step (96), P~ sums by step (85), the H columns' store sinks (DN_SINK..)
                     //        | diag_inverse: T, W staging (256) W' (272) | h_matvec (48)
                     //        | range-space rounds: h_matvec (48), entries (48..120), solves and column vectors (128..512)
+    ldouble* bt;    // 32 x DN_BT_ROW: the leg bases of all 32 face words (basis_table_build, once per QP), row a =
+                    //     leg_basis(a): [T0 T1 T3 T4 T6 T7 up0 up1 up2] -- T's third column and the apex flag follow from
+                    //     the face word (basis_table_read).  The odd row stride puts the 32 rows' element e on 32 different
+                    //     8-byte bank pairs, so lanes reading different face words do not conflict under ds_read_b64
+                    //     (two-way at most where the compiler pairs the loads: 32-dword banking) and equal ones broadcast
     lint* lsm;      // 20: stance leg-step b -> 4k + j
     lint* fb;       // H+1: first stance leg-step of step k
 };
+constexpr int DN_BT_ROW = 9, DN_BT = 32 * DN_BT_ROW;  // the face-set table of leg bases (DSmem::bt)
+static_assert(DN_BT_ROW % 2 == 1, "an odd row stride keeps the 32 rows on 32 different 8-byte bank pairs");
 constexpr int DN_EL = 16 * 17;               // staging of one 16x16 tile, column stride 17
 constexpr int DN_SCR_MIN = 256 + DN_EL;  // diag_inverse: staging of T and W (128 each) | W'
 // condensation's sinks: lane l's predicated-off H stores go to DN_SINK + l + {0, 1, 2, 16, 32}, past the step sums
@@ -188,6 +195,7 @@ __device__ __forceinline__ DSmem dcarve(double* sm, int H) {
     s.xr = p; p += 12 * H;
     s.lhg = p; p += 64;
     s.scr = p; p += DN_SCR_MIN;
+    s.bt = p; p += DN_BT;
     lint* ip = (lint*)p;
     s.lsm = ip;
     s.fb = ip + 20;

@@ -60,6 +60,56 @@ static_assert(48 + 4 * LMPC_SCHUR_KMAX + 2 * LMPC_SCHUR_KMAX + LMPC_SCHUR_KMAX *
                   120 + LMPC_SCHUR_KMAX + 1 <= 128, "range-space scratch layout");
 constexpr int DN_SCHUR_SV = 120;
 
+// Leg bases from the QP's face-set table (DSmem::bt): 1 on, 0 every reader calls leg_basis (the test-only
+// "basisdirect" build, tests/test_gpu_basis_table.py)
+#ifndef LMPC_BASIS_TABLE
+#define LMPC_BASIS_TABLE 1
+#endif
+
+// The face-set table of leg bases.  leg_basis is a function of the 5-bit face word and the context's (mu, f_max)
+// alone, and a lone wave pays its five IEEE 1/sqrt (~3.5 k cycles) whenever one lane calls it; dense_body called it
+// once in every polish round and once more in every range-space round.  Lane a < 32 evaluates leg_basis(a) once per
+// QP -- the function itself, so a row holds the bits a call returns -- and the rounds read their rows from LDS.
+__device__ __forceinline__ void basis_table_build(ldouble* bt, double mu, double fzmax, int lane) {
+    if (lane < 32) {
+        double T[9], up[3];
+        (void)leg_basis(lane, mu, fzmax, T, up);
+        ldouble* r = bt + DN_BT_ROW * lane;
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            r[2 * p] = T[3 * p];
+            r[2 * p + 1] = T[3 * p + 1];
+            r[6 + p] = up[p];
+        }
+    }
+}
+// leg_basis(act, ...) from the table.  Not stored: T's third column, which leg_basis fills only for act = 0 (the
+// identity), and the apex flag.
+__device__ __forceinline__ bool basis_table_read(const ldouble* bt, int act, double T[9], double up[3]) {
+    const int a = act & 31;
+    const ldouble* r = bt + DN_BT_ROW * a;
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+        T[3 * p] = r[2 * p];
+        T[3 * p + 1] = r[2 * p + 1];
+        T[3 * p + 2] = 0.0;
+        up[p] = r[6 + p];
+    }
+    T[8] = a == 0 ? 1.0 : 0.0;
+    return (a & 3) == 3 || (a & 12) == 12;
+}
+// the rounds' leg basis: the table's row, or in the "basisdirect" build the call it replaces
+__device__ __forceinline__ bool dense_leg_basis(const DSmem& S, int act, double mu, double fzmax, double T[9],
+                                                double up[3]) {
+#if LMPC_BASIS_TABLE
+    (void)mu, (void)fzmax;
+    return basis_table_read(S.bt, act, T, up);
+#else
+    (void)S;
+    return leg_basis(act, mu, fzmax, T, up);
+#endif
+}
+
 // nonzero columns of a leg basis (leg_basis puts them first)
 template <typename P>
 __device__ __forceinline__ int ncols3(const P* T) {
@@ -176,6 +226,12 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
     // coupled leg-steps (T != 0) of the current factorised polish round: bit b = leg-step b (uniform)
     unsigned cmask = 0;
     bool apex = false;
+#if LMPC_BASIS_TABLE
+    // the face-set table is built at the QP's first polish round: at the top of the body, behind the contact-byte and
+    // record loads, or after the hand-over test the launch was 0.6-0.9 % slower ("Leg bases from a
+    // face-set table"; profiles/basis_table/ab_place.log)
+    bool bt_built = false;
+#endif
     // Range-space polish rounds (LMPC_POLISH_SCHUR): a round whose active set only adds faces to the set of the last
     // factorised round (bact, per leg-step lane) is that round's equality QP with k more rows A y = d on its
     // coordinates y, so y = y0 - M^-1 A' (A M^-1 A')^-1 (A y0 - d) from the factorisation in hand: k + 1 solves and
@@ -350,7 +406,14 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
             ++prounds;
             apex = false;
             double (&T)[9] = Tn;
-            if (st) apex = leg_basis(act, mu, fzmax, T, upn);
+#if LMPC_BASIS_TABLE
+            if (!bt_built) {  // wave-uniform
+                basis_table_build(S.bt, mu, fzmax, lane);
+                bt_built = true;
+                LMPC_SYNC();
+            }
+#endif
+            if (st) apex = dense_leg_basis(S, act, mu, fzmax, T, upn);
             schur = false;
 #if LMPC_POLISH_SCHUR
             if (have_base && !force_fact) {
@@ -633,7 +696,7 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
                 bool mis = false;
                 if (st && act != bact) {
                     double Tk[9], uk[3];
-                    (void)leg_basis(act & bact, mu, fzmax, Tk, uk);
+                    (void)dense_leg_basis(S, act & bact, mu, fzmax, Tk, uk);
                     mis = ncols3(S.blk + 9 * lane) != leg_free(bact) || ncols3(Tn) != leg_free(act) ||
                           ncols3(Tk) != leg_free(act & bact);
                 }
@@ -644,7 +707,7 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
                 const ldouble* Tb = S.blk + 9 * lane;
                 const ldouble* ub = S.lup + 3 * lane;
                 double Tc[9], uc[3];
-                (void)leg_basis(act & bact, mu, fzmax, Tc, uc);
+                (void)dense_leg_basis(S, act & bact, mu, fzmax, Tc, uc);
                 // new directions: T_c's columns beyond span(T_b) (orthonormal)
                 double tv[3][3];
                 const int nb = ncols3(Tb);

@@ -53,7 +53,7 @@ SCHED_FLAGS = {
 SOURCES = ["lmpc_kernels.hip", "lmpc_lq.hip", "lmpc_fused.hip", "lmpc_dense.hip", "lmpc_gi.hip", "lmpc_prep.hip", "lmpc_rollout.hip", "lmpc_hoqp.hip", "lmpc_wbc.hip", "lmpc_rbd.hip", "lmpc_sim.hip", "lmpc_contact.hip", "lmpc_stack.hip", "lmpc_est.hip", "lmpc_lowlevel.hip", "lmpc_lowsim.hip", "lmpc_capi.cpp",
            "hoqp_capi.cpp", "lmpc_host.cpp", "ConvexQPSolver.cpp"]
 HEADERS = ["lmpc_device.h", "lmpc_common.h", "lmpc_kernel_common.h", "lmpc_dense_common.h", "lmpc_dense_kernel.h", "lmpc_lq_kernel.h",
-           "lmpc_hoqp_device.h", "lmpc_rbd_common.h", "lmpc_sim_common.h", "lmpc_contact_common.h", "lmpc_quad_device.h", "lmpc_sim_device.h", "lmpc_stack_common.h", "lmpc_est_common.h", "lmpc_lowlevel_common.h", "lmpc_lowsim_common.h"]
+           "lmpc_hoqp_device.h", "lmpc_rbd_common.h", "lmpc_sim_common.h", "lmpc_contact_common.h", "lmpc_quad_device.h", "lmpc_sim_device.h", "lmpc_stack_common.h", "lmpc_est_common.h", "lmpc_lowlevel_common.h", "lmpc_lowsim_common.h", "lmpc_launch.h"]
 
 
 def hipcc() -> str:

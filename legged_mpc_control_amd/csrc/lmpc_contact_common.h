@@ -1,8 +1,8 @@
 // lmpc_contact_common.h -- the friction-pyramid contact problem and the plant step of include/lmpc/lmpc_contact.h,
 // written once and compiled for the host (one robot, the feet in a loop: solve_quad() / step_robot() below) and for
-// gfx950 (lmpc_contact.hip: one lane per foot).  It builds on lmpc_sim_common.h (the elimination, K = J M^-1 J' and
-// the 3 x 3 block tools), which it leaves as it is, and has no HIP runtime call: a plain C++ program can include it
-// (tests/cpp/contact_host_check.cpp).
+// gfx950 (lmpc_contact.hip: one lane per foot).  It builds on lmpc_sim_common.h (the elimination, K = J M^-1 J', the
+// 3 x 3 block tools and the plant step's front and back halves, which the two plants share), and has no HIP runtime
+// call: a plain C++ program can include it (tests/cpp/contact_host_check.cpp).
 //
 // The problem, per robot:  min 1/2 P' K P + P' c  over the feet of the mask, |P_x| <= mu P_z, |P_y| <= mu P_z per foot,
 // with the 3 x 3 blocks K_lm of K and c_l = u_free_l + b_l.  The pieces, each a function of one foot (one lane):
@@ -288,93 +288,39 @@ inline int solve_bare(const lmpc_contact_cfg& cfg, const double* Kd, const doubl
     return out.status;
 }
 
-// One plant step (lmpc_sim_common.h's solve_robot() with the contact problem in the place of the unilateral rule).
+// One plant step of the frictional plant: lmpc_sim_common.h's plant_terms() / plant_back() / plant_finish() with the
+// contact problem between them, where solve_robot() has the unilateral rule.
 // Returns the status; on 1, `out` and `cout` are zero and `next` = `st`.  `next` may alias `st`; `cout` may be null.
 inline int step_robot(const lmpc_rbd_model& md, const lmpc_contact_cfg& cfg, const lmpc_rbd_state& st, const double* tau,
                       const int32_t* mask, lmpc_rbd_state* next, lmpc_sim_out& out, lmpc_contact_out* cout) {
     const double dt = cfg.dt;
-    const BaseKin bk = base_kin(st);
-    LegOut g[4];
-    for (int l = 0; l < 4; ++l) leg_pass(md, st, bk, l, g[l]);
-    BaseOut base;
-    base_pass(bk, total_part(trunk_part(md, bk), g[0].sum, g[1].sum, g[2].sum, g[3].sum), base);
-    LegRed r[4];
-    V3 rl[4], c[4], xl[4];
+    PlantTerms t;
+    plant_terms(md, st, tau, dt, true, t);
+    V3 c[4], xl[4];
     bool in[4];
-    bool bad = false;
+    double gap[4], xb[6];
     for (int l = 0; l < 4; ++l) {
-        leg_rhs(g[l], tau + 3 * l, dt, true, rl[l], c[l]);
-        leg_reduce(g[l], rl[l], c[l], r[l]);
-        bad = bad || !r[l].okm;
         in[l] = mask[l] != 0;
-    }
-    double e[NC + 6], yb[6], xb[6];
-    base_entries(base, dt, e);
-    for (int n = 0; n < NC + 6; ++n) e[n] = minus4(e[n], r[0].Cs[n], r[1].Cs[n], r[2].Cs[n], r[3].Cs[n]);
-    Chol6 Ls;
-    bad = !base_factor(e, Ls, yb) || bad;
-    LegRows w[4];
-    for (int l = 0; l < 4; ++l) leg_rows(r[l], Ls, yb, w[l]);
-    Blk K[4][4];
-    for (int m = 0; m < 4; ++m)
-        for (int k = 0; k < 4; ++k) blk_of(w[m].Z, w[k].Z, r[m].A, m == k, K[m][k]);
-    const V3 pos = v3(st.pos[0], st.pos[1], st.pos[2]);
-    double gap[4];
-    for (int l = 0; l < 4; ++l) {
-        gap[l] = (pos.z + g[l].foot.z) - cfg.ground_z;
-        c[l] = contact_c(w[l].rhs, gap[l], cfg.use_gap != 0, cfg.recover_speed, dt);
+        gap[l] = (st.pos[2] + t.g[l].foot.z) - cfg.ground_z;
+        c[l] = contact_c(t.w[l].rhs, gap[l], cfg.use_gap != 0, cfg.recover_speed, dt);
     }
     Sol s;
-    solve_quad(K, c, in, caps_of(cfg), s);
-    bad = bad || s.bad;
-    const V3* P = s.P;
-    double zp[4][6], t[6];
-    for (int l = 0; l < 4; ++l) leg_zp(w[l], P[l], zp[l]);
-    for (int i = 0; i < 6; ++i) t[i] = plus4(yb[i], zp[0][i], zp[1][i], zp[2][i], zp[3][i]);
-    base_back(Ls, t, xb);
-    for (int l = 0; l < 4; ++l) xl[l] = leg_back(g[l], r[l], rl[l], xb, P[l]);
-    for (int i = 0; i < 6; ++i) bad = bad || !finite(xb[i]);
-    for (int l = 0; l < 4; ++l) bad = bad || !finite(xl[l]) || !finite(P[l]) || !finite(s.w[l]);
-    if (bad) {
-        zero_out(out, 1);
-        if (cout) zero_cout(*cout, 1);
-        if (next != &st) *next = st;
-        return 1;
-    }
-    const int status = s.certified ? 0 : 2;
-    zero_out(out, status);
-    BaseNext bn;
-    base_advance(bk, v3(st.euler[0], st.euler[1], st.euler[2]), pos, xb, dt, bn);
-    LegNext ln[4];
-    for (int l = 0; l < 4; ++l)
-        leg_advance(g[l], v3(st.joint_pos[3 * l], st.joint_pos[3 * l + 1], st.joint_pos[3 * l + 2]),
-                    v3(st.joint_vel[3 * l], st.joint_vel[3 * l + 1], st.joint_vel[3 * l + 2]), xl[l], P[l], dt, bn, pos,
-                    ln[l]);
-    lmpc_rbd_state n;
-    n.euler[0] = bn.euler.x, n.euler[1] = bn.euler.y, n.euler[2] = bn.euler.z;
-    n.pos[0] = bn.pos.x, n.pos[1] = bn.pos.y, n.pos[2] = bn.pos.z;
-    n.omega[0] = bn.omega.x, n.omega[1] = bn.omega.y, n.omega[2] = bn.omega.z;
-    n.lin_vel[0] = bn.vlin.x, n.lin_vel[1] = bn.vlin.y, n.lin_vel[2] = bn.vlin.z;
-    for (int i = 0; i < 6; ++i) out.qdd[i] = bn.qdd[i];
+    solve_quad(t.K, c, in, caps_of(cfg), s);
+    bool bad = plant_back(t, s.P, t.bad || s.bad, xb, xl);
+    for (int l = 0; l < 4; ++l) bad = bad || !finite(s.w[l]);
+    const int status = bad ? 1 : (s.certified ? 0 : 2);
+    plant_finish(t, st, true, dt, xb, xl, s.P, status, next, out);
     if (cout) zero_cout(*cout, status);
+    if (bad) return 1;
     for (int l = 0; l < 4; ++l) {
-        const LegNext& a = ln[l];
-        const double jp[3] = {a.jp.x, a.jp.y, a.jp.z}, jv[3] = {a.jv.x, a.jv.y, a.jv.z};
-        const double q[3] = {a.qdd.x, a.qdd.y, a.qdd.z}, F[3] = {a.force.x, a.force.y, a.force.z};
-        const double p[3] = {a.foot_pos.x, a.foot_pos.y, a.foot_pos.z}, v[3] = {a.foot_vel.x, a.foot_vel.y, a.foot_vel.z};
-        const double ws[3] = {s.w[l].x, s.w[l].y, s.w[l].z};
-        for (int i = 0; i < 3; ++i) {
-            n.joint_pos[3 * l + i] = jp[i], n.joint_vel[3 * l + i] = jv[i];
-            out.qdd[6 + 3 * l + i] = q[i], out.force[3 * l + i] = F[i];
-            out.foot_pos[3 * l + i] = p[i], out.foot_vel[3 * l + i] = v[i];
-            if (cout) cout->w[3 * l + i] = ws[i];
-        }
-        out.held[l] = P[l].z > 0.0;
-        out.touch[l] = touch_flag(cfg.touch_rule, a.foot_pos.z, cfg.ground_z, a.force, cfg.force_threshold);
-        if (cout) cout->gap[l] = gap[l], cout->mode[l] = s.mode[l];
+        const V3 force = v3(out.force[3 * l], out.force[3 * l + 1], out.force[3 * l + 2]);
+        out.held[l] = s.P[l].z > 0.0;
+        out.touch[l] = touch_flag(cfg.touch_rule, out.foot_pos[3 * l + 2], cfg.ground_z, force, cfg.force_threshold);
+        if (!cout) continue;
+        cout->w[3 * l] = s.w[l].x, cout->w[3 * l + 1] = s.w[l].y, cout->w[3 * l + 2] = s.w[l].z;
+        cout->gap[l] = gap[l], cout->mode[l] = s.mode[l];
     }
     if (cout) cout->res_primal = s.res_p, cout->res_dual = s.res_d, cout->sweeps = s.sweeps, cout->polish = s.polish;
-    *next = n;
     return status;
 }
 

@@ -24,6 +24,7 @@
 
 #include "lmpc/lmpc_est.h"
 #include "lmpc_est_common.h"
+#include "lmpc_launch.h"
 
 static_assert(sizeof(lmpc_est_sensors) == 296, "lmpc_est_sensors layout (legged_mpc_control_amd/_native.py)");
 static_assert(sizeof(lmpc_est_cfg) == 144, "lmpc_est_cfg layout");
@@ -238,11 +239,7 @@ __global__ void __launch_bounds__(ONE_THREADS)
 }
 #endif
 
-int launch_rc() {
-    const hipError_t e = hipGetLastError();
-    if (e == hipErrorInvalidDeviceFunction || e == hipErrorNoBinaryForGpu) return LMPC_ERR_NOT_BUILT;
-    return e == hipSuccess ? LMPC_OK : LMPC_ERR_LAUNCH;
-}
+using lmpc_launch::launch_rc;
 
 }  // namespace
 }  // namespace lmpc_est
@@ -313,7 +310,7 @@ extern "C" int lmpc_est_sensors_from_plant_device(const lmpc_rbd_model* model, c
     hipLaunchKernelGGL(lmpc_est_sensors_kernel, dim3((batch + ONE_THREADS - 1) / ONE_THREADS), dim3(ONE_THREADS), 0,
                        (hipStream_t)stream, *model, *cfg, d_state, d_sim_out, batch, index0, tick, d_gait,
                        (long long)gait_stride, d_sensors);
-    return launch_rc();
+    return launch_rc(hipGetLastError());
 }
 
 extern "C" int lmpc_est_init_device(const lmpc_rbd_model* model, const lmpc_est_cfg* cfg, const lmpc_est_sensors* d_sensors,
@@ -327,7 +324,7 @@ extern "C" int lmpc_est_init_device(const lmpc_rbd_model* model, const lmpc_est_
     hipLaunchKernelGGL(lmpc_est_init_kernel, dim3((batch + ONE_THREADS - 1) / ONE_THREADS), dim3(ONE_THREADS), 0,
                        (hipStream_t)stream, *model, *cfg, d_sensors, d_pos0, (long long)pos0_stride, batch, d_filter,
                        d_state_est, d_out, d_sim_out, d_shadow);
-    return launch_rc();
+    return launch_rc(hipGetLastError());
 }
 
 extern "C" int lmpc_est_update_device(const lmpc_rbd_model* model, const lmpc_est_cfg* cfg, const lmpc_est_sensors* d_sensors,
@@ -341,5 +338,5 @@ extern "C" int lmpc_est_update_device(const lmpc_rbd_model* model, const lmpc_es
     hipLaunchKernelGGL(lmpc_est_update_kernel, dim3((batch + BLOCK_ROBOTS - 1) / BLOCK_ROBOTS), dim3(BLOCK), 0,
                        (hipStream_t)stream, *model, *cfg, d_sensors, batch, d_filter, d_state_est, d_out, d_sim_out,
                        d_shadow);
-    return launch_rc();
+    return launch_rc(hipGetLastError());
 }

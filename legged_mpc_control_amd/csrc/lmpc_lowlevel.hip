@@ -16,10 +16,14 @@
 #include <cstring>
 
 #include "lmpc/lmpc_lowlevel.h"
+#include "lmpc_launch.h"
 #include "lmpc_lowlevel_common.h"
 
 namespace lmpc_ll {
 namespace {
+
+using lmpc_launch::launch_rc;
+using lmpc_launch::PtrScope;
 
 constexpr int THREADS = 256;
 constexpr int BLOCK_ROBOTS = THREADS / 4;  // one lane per leg
@@ -44,44 +48,6 @@ __global__ void __launch_bounds__(THREADS)
     leg(c, in, mode, o);
     leg_store(o, l, outs[b]);
     if (cand) cand[e] = candidate(sim_outs[b].held[l], sim_outs[b].touch[l]);
-}
-
-// The device a device pointer lives on, or -1.
-int pointer_device(const void* p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return -1;
-    }
-    return a.device;
-}
-
-// Launch context, as lmpc_stack.hip's: the device of `anchor`, the caller's current device restored on return; a
-// non-NULL stream must belong to that device.
-struct PtrScope {
-    int prev = -1, dev = -1;
-    bool ok = false;
-    PtrScope(const void* anchor, hipStream_t s) {
-        if (hipGetDevice(&prev) != hipSuccess) {
-            prev = -1;
-            return;
-        }
-        dev = pointer_device(anchor);
-        if (dev < 0) dev = prev;
-        if (s) {
-            hipDevice_t d = -1;
-            if (hipStreamGetDevice(s, &d) != hipSuccess || d != dev) return;
-        }
-        ok = dev == prev || hipSetDevice(dev) == hipSuccess;
-    }
-    ~PtrScope() {
-        if (prev >= 0 && dev != prev) (void)hipSetDevice(prev);
-    }
-};
-
-int launch_rc(hipError_t e) {
-    if (e == hipErrorInvalidDeviceFunction || e == hipErrorNoBinaryForGpu) return LMPC_ERR_NOT_BUILT;
-    return e == hipSuccess ? LMPC_OK : LMPC_ERR_LAUNCH;
 }
 
 void cfg_preset(lmpc_lowlevel_cfg* c, double kp, double kd) {

@@ -8,7 +8,7 @@
 //                        diverge) on those registers and stores the controller's output and the candidate word at once
 //                        (into the log row; on the last tick into the buffers) -- only tau3 and the candidate bit are
 //                        carried into the plant, which has no registers to spare --
-//                        and then runs `substeps` plant substeps (lmpc_sim::substep, lmpc_sim_device.h), whose quad
+//                        and then runs `substeps` plant substeps (lmpc_sim::step_lane, lmpc_sim_device.h), whose quad
 //                        shuffles all 64 lanes reach together: the controller's branches have rejoined by then, and the
 //                        tick and substep counts are uniform.
 //
@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "lmpc/lmpc_lowsim.h"
+#include "lmpc_launch.h"
 #include "lmpc_lowsim_common.h"
 #include "lmpc_quad_device.h"
 #include "lmpc_sim_device.h"
@@ -25,13 +26,12 @@
 namespace lmpc_lowsim {
 namespace {
 
-constexpr int BLOCK = 64;                // one wavefront per block, as lmpc_sim.hip
-constexpr int BLOCK_ROBOTS = BLOCK / 4;  // one quad of lanes per robot
+using lmpc_sim::BLOCK;
+using lmpc_sim::BLOCK_ROBOTS;
 
 #if defined(__HIPCC__)
 using lmpc_sim::store_out;
 using lmpc_sim::store_state;
-using lmpc_sim::V3;
 
 __global__ void __launch_bounds__(BLOCK)
     lmpc_lowsim_kernel(const lmpc_rbd_model md, const lmpc_lowlevel_cfg cfg, lmpc_rbd_state* states,
@@ -44,16 +44,8 @@ __global__ void __launch_bounds__(BLOCK)
     const bool active = robot < batch;
     const int r = active ? robot : batch - 1;
 
-    // the base's state, and the lane's own joints in slot 0
-    lmpc_rbd_state ls;
-    {
-        const lmpc_rbd_state& st = states[r];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            ls.euler[i] = st.euler[i], ls.pos[i] = st.pos[i], ls.omega[i] = st.omega[i], ls.lin_vel[i] = st.lin_vel[i];
-            ls.joint_pos[i] = st.joint_pos[3 * L + i], ls.joint_vel[i] = st.joint_vel[3 * L + i];
-        }
-    }
+    lmpc_rbd_state ls;  // the base's state, and the lane's own joints in slot 0
+    lmpc_sim::load_lane_state(states[r], L, ls);
     const int mode = gaits && gaits[(long long)r * gait_stride] == LMPC_GAIT_STAND ? 0 : 1;
     // the flags of the plant's last step, from here on in registers
     int32_t held = sim_outs[r].held[L], touch = sim_outs[r].touch[L];
@@ -95,30 +87,17 @@ __global__ void __launch_bounds__(BLOCK)
 
         bool failed = false;  // quad-uniform; every tick starts afresh, as every launch of the unfused loop does
         for (int step = 0; step < substeps; ++step) {
-            double oq[6];
-            V3 oqdd, oforce, ofp, ofv;
+            lmpc_sim::LaneOut o;
             bool h;
             int otouch;
-            lmpc_rbd_state nx;  // a copy in, the state after the substep out (lmpc_sim_device.h)
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                nx.euler[i] = ls.euler[i], nx.pos[i] = ls.pos[i], nx.omega[i] = ls.omega[i], nx.lin_vel[i] = ls.lin_vel[i];
-                nx.joint_pos[i] = ls.joint_pos[i], nx.joint_vel[i] = ls.joint_vel[i];
-            }
-            lmpc_sim::substep<true>(md, L, ls, nx, tau3, cand != 0, dt, ground_z, unilateral, oq, oqdd, oforce, ofp, ofv, h,
-                                    otouch, failed);
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                ls.euler[i] = nx.euler[i], ls.pos[i] = nx.pos[i], ls.omega[i] = nx.omega[i], ls.lin_vel[i] = nx.lin_vel[i];
-                ls.joint_pos[i] = nx.joint_pos[i], ls.joint_vel[i] = nx.joint_vel[i];
-            }
+            lmpc_sim::step_lane<true>(md, L, ls, tau3, cand != 0, dt, ground_z, unilateral, o, h, otouch, failed);
             if (step == substeps - 1) {
                 int ro = r;
                 asm volatile("" : "+v"(ro));
                 const long long row = (long long)tick * batch + ro;
                 held = h && !failed ? 1 : 0, touch = otouch;
-                if (tick == ticks - 1) store_out(sim_outs[ro], oq, oqdd, oforce, ofp, ofv, held, touch, failed, L, active);
-                if (log.outs) store_out(log.outs[row], oq, oqdd, oforce, ofp, ofv, held, touch, failed, L, active);
+                if (tick == ticks - 1) store_out(sim_outs[ro], o, held, touch, failed ? 1 : 0, L, active);
+                if (log.outs) store_out(log.outs[row], o, held, touch, failed ? 1 : 0, L, active);
             }
         }
         if (log.states) {
@@ -131,43 +110,8 @@ __global__ void __launch_bounds__(BLOCK)
 }
 #endif
 
-// The device a device pointer lives on, or -1.
-int pointer_device(const void* p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return -1;
-    }
-    return a.device;
-}
-
-// Launch context, as lmpc_lowlevel.hip's: the device of `anchor`, the caller's current device restored on return; a
-// non-NULL stream must belong to that device.
-struct PtrScope {
-    int prev = -1, dev = -1;
-    bool ok = false;
-    PtrScope(const void* anchor, hipStream_t s) {
-        if (hipGetDevice(&prev) != hipSuccess) {
-            prev = -1;
-            return;
-        }
-        dev = pointer_device(anchor);
-        if (dev < 0) dev = prev;
-        if (s) {
-            hipDevice_t d = -1;
-            if (hipStreamGetDevice(s, &d) != hipSuccess || d != dev) return;
-        }
-        ok = dev == prev || hipSetDevice(dev) == hipSuccess;
-    }
-    ~PtrScope() {
-        if (prev >= 0 && dev != prev) (void)hipSetDevice(prev);
-    }
-};
-
-int launch_rc(hipError_t e) {
-    if (e == hipErrorInvalidDeviceFunction || e == hipErrorNoBinaryForGpu) return LMPC_ERR_NOT_BUILT;
-    return e == hipSuccess ? LMPC_OK : LMPC_ERR_LAUNCH;
-}
+using lmpc_launch::launch_rc;
+using lmpc_launch::PtrScope;
 
 }  // namespace
 }  // namespace lmpc_lowsim
@@ -199,7 +143,7 @@ int lmpc_lowsim_run_device(const lmpc_rbd_model* model, const lmpc_sim_cfg* sim_
     PtrScope ps(d_state, s);
     if (!ps.ok) return LMPC_ERR_ARG;
     const lmpc_lowsim_log lg = log ? *log : lmpc_lowsim_log{nullptr, nullptr, nullptr, nullptr};
-    hipLaunchKernelGGL(lmpc_lowsim_kernel, dim3((unsigned)((batch + BLOCK_ROBOTS - 1) / BLOCK_ROBOTS)), dim3(BLOCK), 0, s,
+    hipLaunchKernelGGL(lmpc_lowsim_kernel, lmpc_sim::quad_grid(batch), dim3(BLOCK), 0, s,
                        *model, *ll_cfg, d_state, d_target, d_gait, (long long)gait_stride, d_sim_out, d_candidates, d_ll_out,
                        batch, ticks, substeps, sim_cfg->dt, sim_cfg->ground_z, (int)sim_cfg->unilateral, lg);
     return launch_rc(hipGetLastError());

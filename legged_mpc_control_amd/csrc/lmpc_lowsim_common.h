@@ -9,7 +9,7 @@
 
 namespace lmpc_lowsim {
 
-inline bool good_dt(double dt) { return dt > 0.0 && lmpc_sim::finite(dt); }
+using lmpc_sim::good_dt;
 
 // lmpc_lowsim_run.  Every tick works on copies, so `ll_out` and the log rows may not overlap the inputs but nothing is
 // read after it was overwritten.

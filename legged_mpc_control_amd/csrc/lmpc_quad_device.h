@@ -1,13 +1,21 @@
 // lmpc_quad_device.h -- the device helpers of the kernels that give a robot one quad of lanes, lane l owning leg l
-// (lmpc_sim.hip, lmpc_contact.hip): values travel between the four lanes by __shfl with width 4, what all four hold
-// identically is stored a quarter per lane, and each lane works on its own leg of the model in slot 0.  Device code
-// only; the arithmetic is lmpc_rbd_common.h's and lmpc_sim_common.h's.
+// (lmpc_rbd.hip, lmpc_sim.hip, lmpc_contact.hip, lmpc_lowsim.hip): the launch layout they share, and the device
+// helpers -- values travel between the four lanes by __shfl with width 4, what all four hold identically is stored a
+// quarter per lane, and each lane works on its own leg of the model in slot 0.  The arithmetic is lmpc_rbd_common.h's
+// and lmpc_sim_common.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "lmpc_sim_common.h"
 
 namespace lmpc_sim {
+// One wavefront per block: 4096 robots are 256 wavefronts, which 64-thread blocks spread over 256 CUs and 256-thread
+// blocks over 64 (measured on lmpc_rbd_kernel, alternating runs: 16.9 us at 64 threads, 18.8 at 128, 22.9 at 256;
+// DESIGN.md 4e).  Lane 4 r + l of a block owns leg l of the block's r-th robot.
+constexpr int BLOCK = 64;
+constexpr int BLOCK_ROBOTS = BLOCK / 4;  // one quad of lanes per robot
+inline dim3 quad_grid(int batch) { return dim3((unsigned)((batch + BLOCK_ROBOTS - 1) / BLOCK_ROBOTS)); }
+
 #if defined(__HIPCC__)
 __device__ inline double quad_get(double v, int l) { return __shfl(v, l, 4); }
 __device__ inline V3 quad_get(const V3& v, int l) { return V3{quad_get(v.x, l), quad_get(v.y, l), quad_get(v.z, l)}; }

@@ -2,13 +2,16 @@
 // the time-stepping integrator, on the host (one robot) and on the device (a batch, four lanes per robot).
 //
 // The arithmetic is lmpc_rbd_common.h's (leg_pass / base_pass) and lmpc_sim_common.h's (the elimination), compiled
-// for both sides.  Device mapping, as lmpc_rbd.hip's: lane 4 r + l of a wavefront owns leg l of the wavefront's r-th
-// robot.  One kernel does everything: the lane runs leg_pass for its leg, the quad exchanges the legs' totals for
-// base_pass, the lane eliminates its leg's joints (27 doubles for the base), the quad exchanges those and every lane
-// factors the same 6 x 6 base block (the same bits in all four); the 12 x 12 J M^-1 J' is spread over the quad, lane l
-// holding block row l, and factored by a block Cholesky whose 3 x 3 blocks travel by quad shuffles; then the lane
-// back-substitutes its own leg.  The unilateral rule repeats only that last factorisation with the shrunken set; the
-// substeps loop with the state in registers.  No LDS, no scratch, no workspace, no 18 x 18 matrix anywhere.
+// for both sides.  The step itself is written in lmpc_sim_common.h (host: solve_robot()) and lmpc_sim_device.h (device:
+// substep()), as halves around the contact solve that lmpc_contact.hip's plant shares; this file holds the kernel's
+// loop and the entry points.  Device mapping, as lmpc_rbd.hip's (lmpc_quad_device.h): lane 4 r + l of a wavefront owns
+// leg l of the wavefront's r-th robot.  One kernel does everything: the lane runs leg_pass for its leg, the quad
+// exchanges the legs' totals for base_pass, the lane eliminates its leg's joints (27 doubles for the base), the quad
+// exchanges those and every lane factors the same 6 x 6 base block (the same bits in all four); the 12 x 12 J M^-1 J'
+// is spread over the quad, lane l holding block row l, and factored by a block Cholesky whose 3 x 3 blocks travel by
+// quad shuffles; then the lane back-substitutes its own leg.  The unilateral rule repeats only that last factorisation
+// with the shrunken set; the substeps loop with the state in registers.  No LDS, no scratch, no workspace, no 18 x 18
+// matrix anywhere.
 //
 // leg_pass indexes the model and the state by the leg's number.  Here each lane copies its leg's part of the model
 // and its own joints into slot 0 of a private model / state and calls leg_pass(..., leg 0): every index is then a
@@ -26,9 +29,6 @@ static_assert(sizeof(lmpc_sim_out) == 472, "lmpc_sim_out layout");
 namespace lmpc_sim {
 namespace {
 
-constexpr int BLOCK = 64;                // one wavefront per block, as lmpc_rbd.hip
-constexpr int BLOCK_ROBOTS = BLOCK / 4;  // one quad of lanes per robot
-
 #if defined(__HIPCC__)
 // STEP = false: the forward dynamics (substeps = 1, dt and ground_z unused, nexts unused).
 template <bool STEP>
@@ -41,16 +41,8 @@ __global__ void __launch_bounds__(BLOCK)
     const bool active = robot < batch;
     const int r = active ? robot : batch - 1;
 
-    // the base's state, and the lane's own joints in slot 0
-    lmpc_rbd_state ls;
-    {
-        const lmpc_rbd_state& st = states[r];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            ls.euler[i] = st.euler[i], ls.pos[i] = st.pos[i], ls.omega[i] = st.omega[i], ls.lin_vel[i] = st.lin_vel[i];
-            ls.joint_pos[i] = st.joint_pos[3 * L + i], ls.joint_vel[i] = st.joint_vel[3 * L + i];
-        }
-    }
+    lmpc_rbd_state ls;  // the base's state, and the lane's own joints in slot 0
+    load_lane_state(states[r], L, ls);
     const double* tp = taus + (long long)r * tau_stride + 3 * L;
     const double tau3[3] = {tp[0], tp[1], tp[2]};
     const bool candidate = contacts[(long long)r * contact_stride + L] != 0;
@@ -60,35 +52,16 @@ __global__ void __launch_bounds__(BLOCK)
     const int nsub = STEP ? substeps : 1;
     for (int step = 0; step < nsub; ++step) {
         // the substep itself: lmpc_sim_device.h (the fused controller + plant kernel of lmpc_lowsim.hip runs the same one)
-        double oq[6];
-        V3 oqdd, oforce, ofp, ofv;
+        LaneOut o;
         bool held;
         int otouch;
-        lmpc_rbd_state nx;  // the state after the substep; the forward dynamics has none
-        if (STEP) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                nx.euler[i] = ls.euler[i], nx.pos[i] = ls.pos[i], nx.omega[i] = ls.omega[i], nx.lin_vel[i] = ls.lin_vel[i];
-                nx.joint_pos[i] = ls.joint_pos[i], nx.joint_vel[i] = ls.joint_vel[i];
-            }
-        }
-        substep<STEP>(md, L, ls, nx, tau3, candidate, dt, ground_z, unilateral, oq, oqdd, oforce, ofp, ofv, held, otouch, failed);
-        if (STEP) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                ls.euler[i] = nx.euler[i], ls.pos[i] = nx.pos[i], ls.omega[i] = nx.omega[i], ls.lin_vel[i] = nx.lin_vel[i];
-                ls.joint_pos[i] = nx.joint_pos[i], ls.joint_vel[i] = nx.joint_vel[i];
-            }
-        }
-        if (outs && step == nsub - 1)
-            store_out(outs[r], oq, oqdd, oforce, ofp, ofv, held && !failed ? 1 : 0, otouch, failed, L, active);
+        step_lane<STEP>(md, L, ls, tau3, candidate, dt, ground_z, unilateral, o, held, otouch, failed);
+        if (outs && step == nsub - 1) store_out(outs[r], o, held && !failed ? 1 : 0, otouch, failed ? 1 : 0, L, active);
     }
 
     if (STEP) store_state(nexts[r], ls, L, active);
 }
 #endif
-
-bool good_dt(double dt) { return dt > 0.0 && finite(dt); }
 
 }  // namespace
 }  // namespace lmpc_sim
@@ -133,7 +106,7 @@ extern "C" int lmpc_rbd_forward_dynamics_device(const lmpc_rbd_model* model, con
                                     contact_stride < 4)))
         return LMPC_ERR_ARG;
     if (batch == 0) return LMPC_OK;
-    hipLaunchKernelGGL((lmpc_sim_kernel<false>), dim3((batch + BLOCK_ROBOTS - 1) / BLOCK_ROBOTS), dim3(BLOCK), 0,
+    hipLaunchKernelGGL((lmpc_sim_kernel<false>), quad_grid(batch), dim3(BLOCK), 0,
                        (hipStream_t)stream, *model, d_state, d_tau, (long long)tau_stride, d_contact,
                        (long long)contact_stride, batch, 1, 0.0, 0.0, unilateral, (lmpc_rbd_state*)nullptr, d_out);
     return hipGetLastError() == hipSuccess ? LMPC_OK : LMPC_ERR_LAUNCH;
@@ -148,7 +121,7 @@ extern "C" int lmpc_sim_step_device(const lmpc_rbd_model* model, const lmpc_sim_
                                     contact_stride < 4 || substeps < 1 || !good_dt(cfg->dt))))
         return LMPC_ERR_ARG;
     if (batch == 0) return LMPC_OK;
-    hipLaunchKernelGGL((lmpc_sim_kernel<true>), dim3((batch + BLOCK_ROBOTS - 1) / BLOCK_ROBOTS), dim3(BLOCK), 0,
+    hipLaunchKernelGGL((lmpc_sim_kernel<true>), quad_grid(batch), dim3(BLOCK), 0,
                        (hipStream_t)stream, *model, d_state, d_tau, (long long)tau_stride, d_contact,
                        (long long)contact_stride, batch, substeps, cfg->dt, cfg->ground_z, (int)cfg->unilateral, d_next,
                        d_out);

@@ -1,6 +1,7 @@
 // lmpc_sim_common.h -- the contact-constrained forward dynamics and the plant step of include/lmpc/lmpc_sim.h, written
-// once and compiled for the host (one robot, the legs in a loop: solve_robot() below) and for gfx950 (lmpc_sim.hip: one
-// lane per leg).  It builds on lmpc_rbd_common.h's leg_pass() / base_pass() and has no HIP runtime call: a plain C++
+// once and compiled for the host (one robot, the legs in a loop: plant_terms() / plant_back() / plant_finish() below,
+// which both plants' host steps are made of -- solve_robot() here, lmpc_contact_common.h's step_robot()) and for gfx950
+// (lmpc_sim_device.h: one lane per leg, the same three pieces).  It builds on lmpc_rbd_common.h's leg_pass() / base_pass() and has no HIP runtime call: a plain C++
 // program can include it (tests/cpp/sim_host_check.cpp).
 //
 // The system, for the increment x (qdd, or v+ - v), the multipliers P (F, or the impulse), s = 1 or dt:
@@ -360,38 +361,118 @@ inline bool solve_contacts(const Blk K[4][4], const V3 rhs[4], const bool held[4
     return ok;
 }
 
-// One forward dynamics (step = false: dt and ground_z unused, `next` untouched) or one plant step.  Returns the
-// status; on 1, `out` is zero and `next` = `st`.  `next` may alias `st`.
+// Steps 1-3 for one robot: everything the contact solve and the back-substitution read.  None of it depends on the
+// contact set, so both plants (solve_robot() below, lmpc_contact_common.h's step_robot()) build it by plant_terms().
+struct PlantTerms {
+    BaseKin bk;
+    LegOut g[4];
+    LegRed r[4];
+    V3 rl[4];
+    Chol6 Ls;
+    double yb[6];
+    LegRows w[4];  // w[l].rhs: the right-hand side of foot l's rows of K
+    Blk K[4][4];   // all sixteen blocks (solve_contacts() reads the lower ones)
+    bool bad;      // a non-positive pivot so far
+};
+// s = 1 (step = false: the forward dynamics) or dt
+inline void plant_terms(const lmpc_rbd_model& md, const lmpc_rbd_state& st, const double* tau, double s, bool step,
+                        PlantTerms& t) {
+    t.bk = base_kin(st);
+    for (int l = 0; l < 4; ++l) leg_pass(md, st, t.bk, l, t.g[l]);
+    BaseOut base;
+    base_pass(t.bk, total_part(trunk_part(md, t.bk), t.g[0].sum, t.g[1].sum, t.g[2].sum, t.g[3].sum), base);
+    t.bad = false;
+    for (int l = 0; l < 4; ++l) {
+        V3 c;
+        leg_rhs(t.g[l], tau + 3 * l, s, step, t.rl[l], c);
+        leg_reduce(t.g[l], t.rl[l], c, t.r[l]);
+        t.bad = t.bad || !t.r[l].okm;
+    }
+    double e[NC + 6];
+    base_entries(base, s, e);
+    for (int n = 0; n < NC + 6; ++n) e[n] = minus4(e[n], t.r[0].Cs[n], t.r[1].Cs[n], t.r[2].Cs[n], t.r[3].Cs[n]);
+    t.bad = !base_factor(e, t.Ls, t.yb) || t.bad;
+    for (int l = 0; l < 4; ++l) leg_rows(t.r[l], t.Ls, t.yb, t.w[l]);
+    for (int m = 0; m < 4; ++m)
+        for (int k = 0; k < 4; ++k) blk_of(t.w[m].Z, t.w[k].Z, t.r[m].A, m == k, t.K[m][k]);
+}
+
+// Step 5 for the multipliers P of either plant's contact solve: xb, xl.  Returns `bad`, or that one of xb, xl, P is not
+// finite.
+inline bool plant_back(const PlantTerms& t, const V3 P[4], bool bad, double xb[6], V3 xl[4]) {
+    double zp[4][6], y[6];
+    for (int l = 0; l < 4; ++l) leg_zp(t.w[l], P[l], zp[l]);
+    for (int i = 0; i < 6; ++i) y[i] = plus4(t.yb[i], zp[0][i], zp[1][i], zp[2][i], zp[3][i]);
+    base_back(t.Ls, y, xb);
+    for (int l = 0; l < 4; ++l) xl[l] = leg_back(t.g[l], t.r[l], t.rl[l], xb, P[l]);
+    for (int i = 0; i < 6; ++i) bad = bad || !finite(xb[i]);
+    for (int l = 0; l < 4; ++l) bad = bad || !finite(xl[l]) || !finite(P[l]);
+    return bad;
+}
+
+// What the solve leaves in `out` and `next`, for either plant.  status 1 (failed): `out` is zero and, when step, `next`
+// = `st`.  Else every field of `out` but held and touch (left 0: the plants' rules for them differ) and, when step, the
+// state after it in `next` (step = false: the forward dynamics, dt unused, `next` untouched).  `next` may alias `st`,
+// which is not read after it is written.  Returns the status.
+inline int plant_finish(const PlantTerms& t, const lmpc_rbd_state& st, bool step, double dt, const double xb[6],
+                        const V3 xl[4], const V3 P[4], int status, lmpc_rbd_state* next, lmpc_sim_out& out) {
+    zero_out(out, status);
+    if (status == 1) {
+        if (step && next != &st) *next = st;
+        return 1;
+    }
+    const V3 pos = v3(st.pos[0], st.pos[1], st.pos[2]);
+    if (!step) {
+        for (int i = 0; i < 6; ++i) out.qdd[i] = xb[i];
+        for (int l = 0; l < 4; ++l) {
+            const V3 fp = add(pos, t.g[l].foot);
+            const double q[3] = {xl[l].x, xl[l].y, xl[l].z}, F[3] = {P[l].x, P[l].y, P[l].z};
+            const double p[3] = {fp.x, fp.y, fp.z}, v[3] = {t.g[l].foot_vel.x, t.g[l].foot_vel.y, t.g[l].foot_vel.z};
+            for (int i = 0; i < 3; ++i) {
+                out.qdd[6 + 3 * l + i] = q[i], out.force[3 * l + i] = F[i];
+                out.foot_pos[3 * l + i] = p[i], out.foot_vel[3 * l + i] = v[i];
+            }
+        }
+        return status;
+    }
+    BaseNext bn;
+    base_advance(t.bk, v3(st.euler[0], st.euler[1], st.euler[2]), pos, xb, dt, bn);
+    lmpc_rbd_state n;
+    n.euler[0] = bn.euler.x, n.euler[1] = bn.euler.y, n.euler[2] = bn.euler.z;
+    n.pos[0] = bn.pos.x, n.pos[1] = bn.pos.y, n.pos[2] = bn.pos.z;
+    n.omega[0] = bn.omega.x, n.omega[1] = bn.omega.y, n.omega[2] = bn.omega.z;
+    n.lin_vel[0] = bn.vlin.x, n.lin_vel[1] = bn.vlin.y, n.lin_vel[2] = bn.vlin.z;
+    for (int i = 0; i < 6; ++i) out.qdd[i] = bn.qdd[i];
+    for (int l = 0; l < 4; ++l) {
+        LegNext a;
+        leg_advance(t.g[l], v3(st.joint_pos[3 * l], st.joint_pos[3 * l + 1], st.joint_pos[3 * l + 2]),
+                    v3(st.joint_vel[3 * l], st.joint_vel[3 * l + 1], st.joint_vel[3 * l + 2]), xl[l], P[l], dt, bn, pos, a);
+        const double jp[3] = {a.jp.x, a.jp.y, a.jp.z}, jv[3] = {a.jv.x, a.jv.y, a.jv.z};
+        const double q[3] = {a.qdd.x, a.qdd.y, a.qdd.z}, F[3] = {a.force.x, a.force.y, a.force.z};
+        const double p[3] = {a.foot_pos.x, a.foot_pos.y, a.foot_pos.z}, v[3] = {a.foot_vel.x, a.foot_vel.y, a.foot_vel.z};
+        for (int i = 0; i < 3; ++i) {
+            n.joint_pos[3 * l + i] = jp[i], n.joint_vel[3 * l + i] = jv[i];
+            out.qdd[6 + 3 * l + i] = q[i], out.force[3 * l + i] = F[i];
+            out.foot_pos[3 * l + i] = p[i], out.foot_vel[3 * l + i] = v[i];
+        }
+    }
+    *next = n;
+    return status;
+}
+
+// One forward dynamics (step = false: dt and ground_z unused, `next` untouched) or one plant step of the default plant:
+// the unilateral rule between plant_terms() and plant_back().  Returns the status; on 1, `out` is zero and `next` =
+// `st`.  `next` may alias `st`.
 inline int solve_robot(const lmpc_rbd_model& md, const lmpc_rbd_state& st, const double* tau, const int32_t* contact,
                        bool unilateral, bool step, double dt, double ground_z, lmpc_rbd_state* next, lmpc_sim_out& out) {
-    const BaseKin bk = base_kin(st);
-    LegOut g[4];
-    for (int l = 0; l < 4; ++l) leg_pass(md, st, bk, l, g[l]);
-    BaseOut base;
-    base_pass(bk, total_part(trunk_part(md, bk), g[0].sum, g[1].sum, g[2].sum, g[3].sum), base);
-    const double s = step ? dt : 1.0;
-    LegRed r[4];
-    V3 rl[4], c[4], xl[4], P[4], rhs[4];
+    PlantTerms t;
+    plant_terms(md, st, tau, step ? dt : 1.0, step, t);
+    V3 rhs[4], P[4], xl[4];
     bool held[4];
-    bool bad = false;
-    for (int l = 0; l < 4; ++l) {
-        leg_rhs(g[l], tau + 3 * l, s, step, rl[l], c[l]);
-        leg_reduce(g[l], rl[l], c[l], r[l]);
-        bad = bad || !r[l].okm;
-        held[l] = contact[l] != 0;
-    }
-    double e[NC + 6], yb[6], xb[6];
-    base_entries(base, s, e);
-    for (int n = 0; n < NC + 6; ++n) e[n] = minus4(e[n], r[0].Cs[n], r[1].Cs[n], r[2].Cs[n], r[3].Cs[n]);
-    Chol6 Ls;
-    bad = !base_factor(e, Ls, yb) || bad;
-    LegRows w[4];
-    for (int l = 0; l < 4; ++l) leg_rows(r[l], Ls, yb, w[l]), rhs[l] = w[l].rhs;
-    Blk K[4][4];
-    for (int m = 0; m < 4; ++m)
-        for (int k = 0; k <= m; ++k) blk_of(w[m].Z, w[k].Z, r[m].A, m == k, K[m][k]);
+    for (int l = 0; l < 4; ++l) rhs[l] = t.w[l].rhs, held[l] = contact[l] != 0;
+    bool bad = t.bad;
     for (int pass = 0; pass < 4; ++pass) {
-        bad = !solve_contacts(K, rhs, held, P) || bad;
+        bad = !solve_contacts(t.K, rhs, held, P) || bad;
         if (bad || !unilateral) break;
         bool released = false;
         for (int l = 0; l < 4; ++l)
@@ -402,62 +483,16 @@ inline int solve_robot(const lmpc_rbd_model& md, const lmpc_rbd_state& st, const
     // candidates): no foot is held, every P is 0, and no further solve is needed
     for (int l = 0; l < 4; ++l)
         if (!held[l]) P[l] = v3(0.0, 0.0, 0.0);
-    double zp[4][6], t[6];
-    for (int l = 0; l < 4; ++l) leg_zp(w[l], P[l], zp[l]);
-    for (int i = 0; i < 6; ++i) t[i] = plus4(yb[i], zp[0][i], zp[1][i], zp[2][i], zp[3][i]);
-    base_back(Ls, t, xb);
-    for (int l = 0; l < 4; ++l) xl[l] = leg_back(g[l], r[l], rl[l], xb, P[l]);
-    for (int i = 0; i < 6; ++i) bad = bad || !finite(xb[i]);
-    for (int l = 0; l < 4; ++l) bad = bad || !finite(xl[l]) || !finite(P[l]);
-    if (bad) {
-        zero_out(out, 1);
-        if (step && next != &st) *next = st;
-        return 1;
-    }
-    zero_out(out, 0);
-    const V3 pos = v3(st.pos[0], st.pos[1], st.pos[2]);
-    if (!step) {
-        for (int i = 0; i < 6; ++i) out.qdd[i] = xb[i];
-        for (int l = 0; l < 4; ++l) {
-            const V3 fp = add(pos, g[l].foot);
-            const double q[3] = {xl[l].x, xl[l].y, xl[l].z}, F[3] = {P[l].x, P[l].y, P[l].z};
-            const double p[3] = {fp.x, fp.y, fp.z}, v[3] = {g[l].foot_vel.x, g[l].foot_vel.y, g[l].foot_vel.z};
-            for (int i = 0; i < 3; ++i) {
-                out.qdd[6 + 3 * l + i] = q[i], out.force[3 * l + i] = F[i];
-                out.foot_pos[3 * l + i] = p[i], out.foot_vel[3 * l + i] = v[i];
-            }
-            out.held[l] = held[l];
-        }
-        return 0;
-    }
-    BaseNext bn;
-    base_advance(bk, v3(st.euler[0], st.euler[1], st.euler[2]), pos, xb, dt, bn);
-    LegNext ln[4];
-    for (int l = 0; l < 4; ++l)
-        leg_advance(g[l], v3(st.joint_pos[3 * l], st.joint_pos[3 * l + 1], st.joint_pos[3 * l + 2]),
-                    v3(st.joint_vel[3 * l], st.joint_vel[3 * l + 1], st.joint_vel[3 * l + 2]), xl[l], P[l], dt, bn, pos,
-                    ln[l]);
-    lmpc_rbd_state n;
-    n.euler[0] = bn.euler.x, n.euler[1] = bn.euler.y, n.euler[2] = bn.euler.z;
-    n.pos[0] = bn.pos.x, n.pos[1] = bn.pos.y, n.pos[2] = bn.pos.z;
-    n.omega[0] = bn.omega.x, n.omega[1] = bn.omega.y, n.omega[2] = bn.omega.z;
-    n.lin_vel[0] = bn.vlin.x, n.lin_vel[1] = bn.vlin.y, n.lin_vel[2] = bn.vlin.z;
-    for (int i = 0; i < 6; ++i) out.qdd[i] = bn.qdd[i];
+    double xb[6];
+    bad = plant_back(t, P, bad, xb, xl);
+    if (plant_finish(t, st, step, dt, xb, xl, P, bad ? 1 : 0, next, out) != 0) return 1;
     for (int l = 0; l < 4; ++l) {
-        const LegNext& a = ln[l];
-        const double jp[3] = {a.jp.x, a.jp.y, a.jp.z}, jv[3] = {a.jv.x, a.jv.y, a.jv.z};
-        const double q[3] = {a.qdd.x, a.qdd.y, a.qdd.z}, F[3] = {a.force.x, a.force.y, a.force.z};
-        const double p[3] = {a.foot_pos.x, a.foot_pos.y, a.foot_pos.z}, v[3] = {a.foot_vel.x, a.foot_vel.y, a.foot_vel.z};
-        for (int i = 0; i < 3; ++i) {
-            n.joint_pos[3 * l + i] = jp[i], n.joint_vel[3 * l + i] = jv[i];
-            out.qdd[6 + 3 * l + i] = q[i], out.force[3 * l + i] = F[i];
-            out.foot_pos[3 * l + i] = p[i], out.foot_vel[3 * l + i] = v[i];
-        }
         out.held[l] = held[l];
-        out.touch[l] = a.foot_pos.z <= ground_z;
+        if (step) out.touch[l] = out.foot_pos[3 * l + 2] <= ground_z;
     }
-    *next = n;
     return 0;
 }
+
+inline bool good_dt(double dt) { return dt > 0.0 && finite(dt); }
 
 }  // namespace lmpc_sim

@@ -19,6 +19,7 @@
 #include <cstring>
 
 #include "lmpc/lmpc_stack.h"
+#include "lmpc_launch.h"
 #include "lmpc_stack_common.h"
 
 namespace lmpc {
@@ -107,47 +108,8 @@ hipError_t launch_stack_advance(double dt, const lmpc_rollout_cfg& cfg, lmpc_sta
 
 }  // namespace lmpc
 
-namespace {
-
-// The device a device pointer lives on, or -1.
-int pointer_device(const void* p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return -1;
-    }
-    return a.device;
-}
-
-// Launch context of the entry points that take no MPC context: the device of `anchor` (a device buffer of the call),
-// the caller's current device restored on return; a non-NULL stream must belong to that device.
-struct PtrScope {
-    int prev = -1, dev = -1;
-    bool ok = false;
-    PtrScope(const void* anchor, hipStream_t s) {
-        if (hipGetDevice(&prev) != hipSuccess) {
-            prev = -1;
-            return;
-        }
-        dev = pointer_device(anchor);
-        if (dev < 0) dev = prev;
-        if (s) {
-            hipDevice_t d = -1;
-            if (hipStreamGetDevice(s, &d) != hipSuccess || d != dev) return;
-        }
-        ok = dev == prev || hipSetDevice(dev) == hipSuccess;
-    }
-    ~PtrScope() {
-        if (prev >= 0 && dev != prev) (void)hipSetDevice(prev);
-    }
-};
-
-int launch_rc(hipError_t e) {
-    if (e == hipErrorInvalidDeviceFunction || e == hipErrorNoBinaryForGpu) return LMPC_ERR_NOT_BUILT;
-    return e == hipSuccess ? LMPC_OK : LMPC_ERR_LAUNCH;
-}
-
-}  // namespace
+using lmpc_launch::launch_rc;
+using lmpc_launch::PtrScope;
 
 extern "C" {
 

@@ -265,12 +265,18 @@ def test_argument_checks():
 
 
 def test_kernels_have_no_scratch():
-    """lmpc_lowsim_kernel and both lmpc_sim_kernel instances, cross-compiled with the product's flags: no scratch and no
-    spilled VGPR.  The fused kernel owes that to a compiler option and two opaque indices (build.py): a
-    compiler upgrade that brings the spills back changes no result, so only this test would notice."""
+    """lmpc_lowsim_kernel, both lmpc_sim_kernel instances and the contact kernels of the three-launch step (the bare solve
+    and the step kernel's TERMS and APPLY instances, template arguments 1 and 2; the fused instance, argument 0, spills by
+    design), cross-compiled with the product's flags: no scratch and no spilled VGPR.  They share one front and one back
+    half of the plant step (lmpc_sim_device.h); the fused controller + plant kernel also owes it to a compiler option and
+    two opaque indices (build.py).  A compiler upgrade that brings the spills back changes no result, so
+    only this test would notice."""
     from legged_mpc_control_amd import build as B
 
-    for source, pattern, count in (("lmpc_lowsim.hip", "lmpc_lowsim_kernel", 1), ("lmpc_sim.hip", "lmpc_sim_kernel", 2)):
+    for source, pattern, count in (("lmpc_lowsim.hip", "lmpc_lowsim_kernel", 1), ("lmpc_sim.hip", "lmpc_sim_kernel", 2),
+                                   ("lmpc_contact.hip", "lmpc_contact_solve_kernel", 1),
+                                   ("lmpc_contact.hip", "lmpc_contact_step_kernelILi1E", 1),
+                                   ("lmpc_contact.hip", "lmpc_contact_step_kernelILi2E", 1)):
         meta = {k: v for k, v in B.device_metadata(source).items() if pattern in k}
         assert len(meta) == count, (source, list(meta))
         for name, m in meta.items():

@@ -1,6 +1,7 @@
 """In-tree build of the HIP library (hipcc, gfx950 only) and the C++ host mirror test."""
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -52,8 +53,16 @@ SCHED_FLAGS = {
 
 SOURCES = ["lmpc_kernels.hip", "lmpc_lq.hip", "lmpc_fused.hip", "lmpc_dense.hip", "lmpc_gi.hip", "lmpc_prep.hip", "lmpc_rollout.hip", "lmpc_hoqp.hip", "lmpc_wbc.hip", "lmpc_rbd.hip", "lmpc_sim.hip", "lmpc_contact.hip", "lmpc_stack.hip", "lmpc_est.hip", "lmpc_lowlevel.hip", "lmpc_lowsim.hip", "lmpc_capi.cpp",
            "hoqp_capi.cpp", "lmpc_host.cpp", "ConvexQPSolver.cpp"]
-HEADERS = ["lmpc_device.h", "lmpc_common.h", "lmpc_kernel_common.h", "lmpc_dense_common.h", "lmpc_dense_kernel.h", "lmpc_lq_kernel.h",
-           "lmpc_hoqp_device.h", "lmpc_rbd_common.h", "lmpc_sim_common.h", "lmpc_contact_common.h", "lmpc_quad_device.h", "lmpc_sim_device.h", "lmpc_stack_common.h", "lmpc_est_common.h", "lmpc_lowlevel_common.h", "lmpc_lowsim_common.h", "lmpc_launch.h"]
+
+
+def _headers() -> list:
+    """Every header a source of the library may include: csrc/*.h and the public include/lmpc/*, listed from the
+    directories, so that a new header cannot be forgotten and leave a stale library behind."""
+    return sorted(glob.glob(os.path.join(CSRC, "*.h"))) + sorted(glob.glob(os.path.join(ROOT, "include", "lmpc", "*")))
+
+
+def _library_deps() -> list:
+    return [os.path.join(CSRC, s) for s in SOURCES] + _headers()
 
 
 def hipcc() -> str:
@@ -112,9 +121,7 @@ def device_metadata(source: str) -> dict:
     import re
 
     asm = os.path.join(LIBDIR, "build", source + ".s")  # kept: compiled again only when a source or header is newer
-    deps = [os.path.join(CSRC, source), os.path.abspath(__file__)] + [os.path.join(CSRC, h) for h in HEADERS] + \
-        [os.path.join(ROOT, "include", "lmpc", h) for h in os.listdir(os.path.join(ROOT, "include", "lmpc"))]
-    if _stale(asm, deps):
+    if _stale(asm, [os.path.join(CSRC, source), os.path.abspath(__file__)] + _headers()):
         os.makedirs(os.path.dirname(asm), exist_ok=True)
         subprocess.run(_compile_cmd(source, ["--cuda-device-only", "-S", "-o", asm + ".tmp"],
                                     flags=["-Wno-unused-command-line-argument"]), check=True)
@@ -135,16 +142,7 @@ def device_metadata(source: str) -> dict:
 
 
 def build_native(force: bool = False, verbose: bool = False) -> str:
-    srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC, h) for h in HEADERS] + [
-        os.path.join(ROOT, "include", "lmpc", "lmpc.h"), os.path.join(ROOT, "include", "lmpc", "lmpc_hoqp.h"),
-        os.path.join(ROOT, "include", "lmpc", "lmpc_rollout.h"), os.path.join(ROOT, "include", "lmpc", "lmpc_rbd.h"),
-        os.path.join(ROOT, "include", "lmpc", "lmpc_sim.h"), os.path.join(ROOT, "include", "lmpc", "lmpc_stack.h"),
-        os.path.join(ROOT, "include", "lmpc", "lmpc_est.h"), os.path.join(ROOT, "include", "lmpc", "lmpc_contact.h"),
-        os.path.join(ROOT, "include", "lmpc", "lmpc_lowlevel.h"), os.path.join(ROOT, "include", "lmpc", "lmpc_lowsim.h"),
-        os.path.join(ROOT, "include", "lmpc", "ConvexQPSolver.hpp"),
-        os.path.abspath(__file__)]
-    if not force and not _stale(LIB, deps):
+    if not force and not _stale(LIB, _library_deps() + [os.path.abspath(__file__)]):
         return LIB
     return _compile_lib(LIB, os.path.join(LIBDIR, "obj"), verbose=verbose)
 
@@ -172,19 +170,14 @@ def build_multi(force: bool = False, verbose: bool = False) -> str:
 
 def build_stamps(force: bool = False) -> str:
     """Diagnostic library with in-kernel phase cycle stamps (tools/stamps_probe.py); never shipped as the product."""
-    srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    out = os.path.join(ROOT, "tools", "build", "liblmpc_stamps.so")
-    if not force and not _stale(out, srcs + [os.path.join(CSRC, h) for h in HEADERS]):
-        return out
-    return _compile_lib(out, os.path.join(ROOT, "tools", "build", "obj_stamps"), defines=["LMPC_STAMPS"])
+    return build_variant("stamps", ["LMPC_STAMPS"], force)
 
 
 def build_variant(tag: str, defines, force: bool = False, flags=()) -> str:
     """Diagnostic library variant (extra -D flags, extra compiler flags) under tools/build/; never shipped as the
     product."""
-    srcs = [os.path.join(CSRC, s) for s in SOURCES]
     out = os.path.join(ROOT, "tools", "build", f"liblmpc_{tag}.so")
-    if not force and not _stale(out, srcs + [os.path.join(CSRC, h) for h in HEADERS]):
+    if not force and not _stale(out, _library_deps()):
         return out
     return _compile_lib(out, os.path.join(ROOT, "tools", "build", f"obj_{tag}"), defines=defines, flags=flags)
 
@@ -223,67 +216,54 @@ def build_test_variants(force: bool = False) -> dict:
     out = {}
     for tag, (defines, only) in TEST_VARIANTS.items():
         path = os.path.join(TEST_BUILD, f"liblmpc_{tag}.so")
-        deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, h) for h in HEADERS] + [LIB]
-        if force or _stale(path, deps):
+        if force or _stale(path, _library_deps() + [LIB]):
             _compile_lib(path, os.path.join(TEST_BUILD, f"obj_{tag}"), defines=defines, only=only)
         out[tag] = path
     return out
 
 
-def build_cpp_test(force: bool = False) -> str:
-    """C++ program that drives legged::ConvexQPSolver exactly like ConvexMpc::grf_update."""
-    src = os.path.join(ROOT, "tests", "cpp", "grf_update_test.cpp")
-    out = os.path.join(ROOT, "tests", "cpp", "build", "grf_update_test")
-    if not force and not _stale(out, [src, LIB]):
+def _build_program(src: str, out: str, force: bool, deps=(), flags=(), includes=(), libs=("-llmpc",)) -> str:
+    """A C++ program over liblmpc.so (found at run time where it was built); `deps`: what else it is made from,
+    `includes`: directories searched before include/, `libs`: what it links from lib/."""
+    if not force and not _stale(out, [src, LIB] + list(deps)):
         return out
     os.makedirs(os.path.dirname(out), exist_ok=True)
-    cmd = [hipcc(), "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-o", out, src,
-           "-L", LIBDIR, "-llmpc", f"-Wl,-rpath,{LIBDIR}"]
+    cmd = [hipcc(), "-O2", "-std=c++17"] + list(flags) + [a for i in includes for a in ("-I", i)] + \
+        ["-I", os.path.join(ROOT, "include"), "-o", out, src, "-L", LIBDIR] + list(libs) + [f"-Wl,-rpath,{LIBDIR}"]
     subprocess.run(cmd, check=True)
     return out
+
+
+def _cpp_test(name: str, force: bool, **kw) -> str:
+    return _build_program(os.path.join(ROOT, "tests", "cpp", f"{name}.cpp"),
+                          os.path.join(ROOT, "tests", "cpp", "build", name), force, **kw)
+
+
+def build_cpp_test(force: bool = False) -> str:
+    """C++ program that drives legged::ConvexQPSolver exactly like ConvexMpc::grf_update."""
+    return _cpp_test("grf_update_test", force)
 
 
 def build_cpp_multi_test(force: bool = False) -> str:
     """C++ host over the multi-device C-ABI (tests/cpp/multi_test.cpp): shards a batch without PyTorch."""
-    src = os.path.join(ROOT, "tests", "cpp", "multi_test.cpp")
-    out = os.path.join(ROOT, "tests", "cpp", "build", "multi_test")
-    if not force and not _stale(out, [src, LIB, MULTI_LIB]):
-        return out
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    cmd = [hipcc(), "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-o", out, src,
-           "-L", LIBDIR, "-llmpc_multi", "-llmpc", f"-Wl,-rpath,{LIBDIR}"]
-    subprocess.run(cmd, check=True)
-    return out
+    return _cpp_test("multi_test", force, deps=[MULTI_LIB], libs=("-llmpc_multi", "-llmpc"))
 
 
 def build_cpp_eigen_test(force: bool = False) -> str:
     """The reference's ConvexMpc lines over include/lmpc/ConvexQPSolverEigen.hpp (tests/cpp/eigen_dropin_test.cpp),
     compiled against the test stand-ins in tests/cpp/eigen_dropin/ (no Eigen / ROS in this image)."""
-    src = os.path.join(ROOT, "tests", "cpp", "eigen_dropin_test.cpp")
-    stub = os.path.join(ROOT, "tests", "cpp", "eigen_dropin")
-    out = os.path.join(ROOT, "tests", "cpp", "build", "eigen_dropin_test")
-    hdr = os.path.join(ROOT, "include", "lmpc", "ConvexQPSolverEigen.hpp")
-    if not force and not _stale(out, [src, hdr, LIB]):
-        return out
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    cmd = [hipcc(), "-O2", "-std=c++17", "-Wall", "-I", stub, "-I", os.path.join(ROOT, "include"), "-o", out, src,
-           "-L", LIBDIR, "-llmpc", f"-Wl,-rpath,{LIBDIR}"]
-    subprocess.run(cmd, check=True)
-    return out
+    return _cpp_test("eigen_dropin_test", force, deps=[os.path.join(ROOT, "include", "lmpc", "ConvexQPSolverEigen.hpp")],
+                     flags=["-Wall"], includes=[os.path.join(ROOT, "tests", "cpp", "eigen_dropin")])
 
 
 def build_cpp_hoqp_test(force: bool = False) -> str:
     """C++ program running the reference's HoQp test (ho_qp_test.cpp) against legged::HoQp (include/lmpc/HoQp.hpp)."""
-    src = os.path.join(ROOT, "tests", "cpp", "ho_qp_test.cpp")
-    out = os.path.join(ROOT, "tests", "cpp", "build", "ho_qp_test")
-    hdr = os.path.join(ROOT, "include", "lmpc", "HoQp.hpp")
-    if not force and not _stale(out, [src, hdr, LIB]):
-        return out
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    cmd = [hipcc(), "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-o", out, src,
-           "-L", LIBDIR, "-llmpc", f"-Wl,-rpath,{LIBDIR}"]
-    subprocess.run(cmd, check=True)
-    return out
+    return _cpp_test("ho_qp_test", force, deps=[os.path.join(ROOT, "include", "lmpc", "HoQp.hpp")])
+
+
+def build_tool_cpp(name: str, force: bool = False) -> str:
+    """Dev tool program over liblmpc.so (tools/<name>.cpp -> tools/build/<name>); never shipped."""
+    return _build_program(os.path.join(ROOT, "tools", f"{name}.cpp"), os.path.join(ROOT, "tools", "build", name), force)
 
 
 def host_cxx() -> str:
@@ -294,13 +274,13 @@ def host_cxx() -> str:
     raise RuntimeError("no host C++ compiler found")
 
 
-def build_cpp_sim_check(force: bool = False) -> str:
-    """Stand-alone program over csrc/lmpc_sim_common.h (tests/cpp/sim_host_check.cpp), built by the host compiler with
-    AddressSanitizer and UBSan: host code only, no HIP and no liblmpc.so."""
-    src = os.path.join(ROOT, "tests", "cpp", "sim_host_check.cpp")
-    out = os.path.join(ROOT, "tests", "cpp", "build", "sim_host_check")
-    deps = [src, os.path.join(CSRC, "lmpc_sim_common.h"), os.path.join(CSRC, "lmpc_rbd_common.h"),
-            os.path.join(ROOT, "include", "lmpc", "lmpc_sim.h"), os.path.join(ROOT, "include", "lmpc", "lmpc_rbd.h")]
+def _build_host_check(name: str, csrc_headers, public_headers, force: bool) -> str:
+    """tests/cpp/<name>.cpp, a stand-alone program over the named csrc/ and include/lmpc/ headers, built by the host
+    compiler with AddressSanitizer and UBSan: host code only, no HIP and no liblmpc.so."""
+    src = os.path.join(ROOT, "tests", "cpp", f"{name}.cpp")
+    out = os.path.join(ROOT, "tests", "cpp", "build", name)
+    deps = [src] + [os.path.join(CSRC, h) for h in csrc_headers] + \
+        [os.path.join(ROOT, "include", "lmpc", h) for h in public_headers]
     if not force and not _stale(out, deps):
         return out
     os.makedirs(os.path.dirname(out), exist_ok=True)
@@ -308,85 +288,43 @@ def build_cpp_sim_check(force: bool = False) -> str:
            "-Wno-unknown-pragmas", "-I", os.path.join(ROOT, "include"), "-I", CSRC, "-o", out, src]
     subprocess.run(cmd, check=True)
     return out
+
+
+def build_cpp_sim_check(force: bool = False) -> str:
+    """The plant step of csrc/lmpc_sim_common.h on a few robots (tests/cpp/sim_host_check.cpp)."""
+    return _build_host_check("sim_host_check", ("lmpc_sim_common.h", "lmpc_rbd_common.h"), ("lmpc_sim.h", "lmpc_rbd.h"), force)
 
 
 def build_cpp_contact_check(force: bool = False) -> str:
-    """Stand-alone program over csrc/lmpc_contact_common.h (tests/cpp/contact_host_check.cpp), built by the host
-    compiler with AddressSanitizer and UBSan: host code only, no HIP and no liblmpc.so."""
-    src = os.path.join(ROOT, "tests", "cpp", "contact_host_check.cpp")
-    out = os.path.join(ROOT, "tests", "cpp", "build", "contact_host_check")
-    deps = [src] + [os.path.join(CSRC, h) for h in ("lmpc_contact_common.h", "lmpc_sim_common.h", "lmpc_rbd_common.h")] + \
-        [os.path.join(ROOT, "include", "lmpc", h) for h in ("lmpc_contact.h", "lmpc_sim.h", "lmpc_rbd.h")]
-    if not force and not _stale(out, deps):
-        return out
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    cmd = [host_cxx(), "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           "-Wno-unknown-pragmas", "-I", os.path.join(ROOT, "include"), "-I", CSRC, "-o", out, src]
-    subprocess.run(cmd, check=True)
-    return out
+    """The contact model of csrc/lmpc_contact_common.h (tests/cpp/contact_host_check.cpp)."""
+    return _build_host_check("contact_host_check", ("lmpc_contact_common.h", "lmpc_sim_common.h", "lmpc_rbd_common.h"),
+                             ("lmpc_contact.h", "lmpc_sim.h", "lmpc_rbd.h"), force)
 
 
 def build_cpp_est_check(force: bool = False) -> str:
-    """Stand-alone program over csrc/lmpc_est_common.h (tests/cpp/est_host_check.cpp), built by the host compiler with
-    AddressSanitizer and UBSan: host code only, no HIP and no liblmpc.so."""
-    src = os.path.join(ROOT, "tests", "cpp", "est_host_check.cpp")
-    out = os.path.join(ROOT, "tests", "cpp", "build", "est_host_check")
-    deps = [src] + [os.path.join(CSRC, h) for h in ("lmpc_est_common.h", "lmpc_rbd_common.h", "lmpc_common.h")] + \
-        [os.path.join(ROOT, "include", "lmpc", h) for h in ("lmpc_est.h", "lmpc_sim.h", "lmpc_rbd.h")]
-    if not force and not _stale(out, deps):
-        return out
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    cmd = [host_cxx(), "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           "-Wno-unknown-pragmas", "-I", os.path.join(ROOT, "include"), "-I", CSRC, "-o", out, src]
-    subprocess.run(cmd, check=True)
-    return out
+    """The estimator of csrc/lmpc_est_common.h (tests/cpp/est_host_check.cpp)."""
+    return _build_host_check("est_host_check", ("lmpc_est_common.h", "lmpc_rbd_common.h", "lmpc_common.h"),
+                             ("lmpc_est.h", "lmpc_sim.h", "lmpc_rbd.h"), force)
 
 
 def build_cpp_lowlevel_check(force: bool = False) -> str:
-    """Stand-alone program over csrc/lmpc_lowlevel_common.h (tests/cpp/lowlevel_host_check.cpp), built by the host
-    compiler with AddressSanitizer and UBSan: host code only, no HIP and no liblmpc.so."""
-    src = os.path.join(ROOT, "tests", "cpp", "lowlevel_host_check.cpp")
-    out = os.path.join(ROOT, "tests", "cpp", "build", "lowlevel_host_check")
-    deps = [src] + [os.path.join(CSRC, h) for h in ("lmpc_lowlevel_common.h", "lmpc_common.h")] + \
-        [os.path.join(ROOT, "include", "lmpc", h) for h in ("lmpc_lowlevel.h", "lmpc_sim.h", "lmpc_rbd.h", "lmpc.h")]
-    if not force and not _stale(out, deps):
-        return out
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    cmd = [host_cxx(), "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           "-Wno-unknown-pragmas", "-I", os.path.join(ROOT, "include"), "-I", CSRC, "-o", out, src]
-    subprocess.run(cmd, check=True)
-    return out
+    """The joint-PD controller of csrc/lmpc_lowlevel_common.h (tests/cpp/lowlevel_host_check.cpp)."""
+    return _build_host_check("lowlevel_host_check", ("lmpc_lowlevel_common.h", "lmpc_common.h"),
+                             ("lmpc_lowlevel.h", "lmpc_sim.h", "lmpc_rbd.h", "lmpc.h"), force)
 
 
 def build_cpp_lowsim_check(force: bool = False) -> str:
-    """Stand-alone program over csrc/lmpc_lowsim_common.h (tests/cpp/lowsim_host_check.cpp): lmpc_lowsim_run's host
-    function against the explicit loop of controller and plant steps, built by the host compiler with AddressSanitizer and UBSan: host code only, no HIP and no liblmpc.so."""
-    src = os.path.join(ROOT, "tests", "cpp", "lowsim_host_check.cpp")
-    out = os.path.join(ROOT, "tests", "cpp", "build", "lowsim_host_check")
-    deps = [src] + [os.path.join(CSRC, h) for h in ("lmpc_lowlevel_common.h", "lmpc_sim_common.h", "lmpc_rbd_common.h",
-                                                    "lmpc_common.h", "lmpc_lowsim_common.h")] + \
-        [os.path.join(ROOT, "include", "lmpc", h) for h in ("lmpc_lowsim.h", "lmpc_lowlevel.h", "lmpc_sim.h", "lmpc_rbd.h",
-                                                            "lmpc.h")]
-    if not force and not _stale(out, deps):
-        return out
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    cmd = [host_cxx(), "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           "-Wno-unknown-pragmas", "-I", os.path.join(ROOT, "include"), "-I", CSRC, "-o", out, src]
-    subprocess.run(cmd, check=True)
-    return out
+    """lmpc_lowsim_run's host function (csrc/lmpc_lowsim_common.h) against the explicit loop of controller and plant
+    steps (tests/cpp/lowsim_host_check.cpp)."""
+    return _build_host_check("lowsim_host_check", ("lmpc_lowlevel_common.h", "lmpc_sim_common.h", "lmpc_rbd_common.h",
+                                                   "lmpc_common.h", "lmpc_lowsim_common.h"),
+                             ("lmpc_lowsim.h", "lmpc_lowlevel.h", "lmpc_sim.h", "lmpc_rbd.h", "lmpc.h"), force)
 
 
-def build_tool_cpp(name: str, force: bool = False) -> str:
-    """Dev tool program over liblmpc.so (tools/<name>.cpp -> tools/build/<name>); never shipped."""
-    src = os.path.join(ROOT, "tools", f"{name}.cpp")
-    out = os.path.join(ROOT, "tools", "build", name)
-    if not force and not _stale(out, [src, LIB]):
-        return out
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    cmd = [hipcc(), "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-o", out, src,
-           "-L", LIBDIR, "-llmpc", f"-Wl,-rpath,{LIBDIR}"]
-    subprocess.run(cmd, check=True)
-    return out
+def build_cpp_order_check(force: bool = False) -> str:
+    """The cross-stream ordering and the grown buffer of csrc/lmpc_order.h over a logging stand-in for HIP
+    (tests/cpp/order_host_check.cpp)."""
+    return _build_host_check("order_host_check", ("lmpc_order.h",), ("lmpc.h",), force)
 
 
 if __name__ == "__main__":

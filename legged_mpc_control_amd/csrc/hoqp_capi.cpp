@@ -10,6 +10,11 @@
 
 #include "lmpc/lmpc_hoqp.h"
 #include "lmpc_hoqp_device.h"
+#include "lmpc_launch.h"
+
+using lmpc_launch::DeviceBuffer;
+using lmpc_launch::DeviceScope;
+using lmpc_launch::stream_ok;
 
 namespace lmpc {
 hipError_t launch_hoqp(const HoqpDev& P, const double* rec, int batch, double* x, double* w, int32_t* status,
@@ -25,39 +30,15 @@ struct lmpc_hoqp_ctx {
     double* d_rec = nullptr;    // host path staging: records
     double* d_out = nullptr;    // host path staging: x | slack
     int32_t* d_st = nullptr;    // host path staging: status | iters
-    double* d_scratch = nullptr;  // per-instance Z, Z', A'A, grown on demand
-    size_t scratch_inst = 0;
-    double* d_z = nullptr;      // host path staging: stacked Z matrices + column counts (allocated on first use)
-    int32_t* d_zc = nullptr;
-    unsigned long long* d_act = nullptr;  // host path staging: active-set blocks (allocated on first warm use)
-    // orders launches that share d_scratch across streams: recorded on the last launch's stream only when the next
-    // one comes on another stream (as lmpc_capi.cpp, round 6: back-to-back launches on one stream pay no event);
-    // host-side waits (scratch growth, lmpc_hoqp_sync, lmpc_hoqp_destroy) wait for the device instead
-    hipEvent_t ev = nullptr;
-    hipStream_t ev_stream = nullptr;
-    bool ev_live = false;
-    hipStream_t last = nullptr;
-    bool pend = false;
+    DeviceBuffer<double> scratch;  // per-instance Z, Z', A'A, grown on demand
+    DeviceBuffer<double> z;        // host path staging: stacked Z matrices + column counts (allocated on first use)
+    DeviceBuffer<int32_t> zc;
+    DeviceBuffer<unsigned long long> act;  // host path staging: active-set blocks (allocated on first warm use)
+    // orders the launches that share the scratch across streams, and the host's waits for them (lmpc_order.h)
+    lmpc_launch::Order order;
 };
 
 namespace {
-
-struct DeviceScope {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceScope(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) {
-            prev = -1;
-            return;
-        }
-        ok = prev == dev || hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-    DeviceScope(const DeviceScope&) = delete;
-    DeviceScope& operator=(const DeviceScope&) = delete;
-};
 
 void fill_dev(lmpc::HoqpDev& P, const lmpc_hoqp_dims* d);
 
@@ -110,46 +91,14 @@ void fill_dev(lmpc::HoqpDev& P, const lmpc_hoqp_dims* d) {
     P.act_len = lmpc::HQ_ACT_WORDS * P.L;
 }
 
-hipError_t ensure_scratch(lmpc_hoqp_ctx* c, int batch) {
-    if ((size_t)batch <= c->scratch_inst) return hipSuccess;
-    double* p = nullptr;
-    hipError_t e = hipMalloc(&p, (size_t)batch * c->P.scratch_len * sizeof(double));
-    if (e != hipSuccess) return e;
-    if (c->d_scratch) {
-        // an earlier launch on another stream may still use the old block
-        if (c->pend) (void)hipDeviceSynchronize();
-        else if (c->ev_live) (void)hipEventSynchronize(c->ev);
-        c->pend = false;
-        (void)hipFree(c->d_scratch);
-    }
-    c->d_scratch = p;
-    c->scratch_inst = (size_t)batch;
-    return hipSuccess;
-}
-
-bool stream_ok(hipStream_t s, int dev) {
-    if (!s) return true;
-    hipDevice_t d = -1;
-    return hipStreamGetDevice(s, &d) == hipSuccess && d == dev;
-}
+int ensure_scratch(lmpc_hoqp_ctx* c, int batch) { return c->scratch.grow((size_t)batch * c->P.scratch_len); }
 
 hipError_t launch(lmpc_hoqp_ctx* c, const double* rec, int batch, double* x, double* w, int32_t* st, int32_t* it,
                   double* z, int32_t* zc, unsigned long long* act, hipStream_t s) {
-    hipError_t e = ensure_scratch(c, batch);
-    if (e != hipSuccess) return e;
-    if (c->pend && c->last != s) {
-        e = hipEventRecord(c->ev, c->last);
-        c->pend = false;
-        c->ev_stream = c->last;
-        c->ev_live = e == hipSuccess;
-        if (e != hipSuccess) return e;
-    }
-    if (!(c->pend && c->last == s) && c->ev_live && c->ev_stream != s && (e = hipStreamWaitEvent(s, c->ev, 0)) != hipSuccess)
-        return e;
-    e = lmpc::launch_hoqp(c->P, rec, batch, x, w, st, it, z, zc, c->d_scratch, act, s);
-    if (e != hipSuccess) return e;
-    c->last = s;
-    c->pend = true;
+    if (ensure_scratch(c, batch) != LMPC_OK) return hipErrorOutOfMemory;
+    hipError_t e = c->order.enter(s);
+    if (e == hipSuccess) e = lmpc::launch_hoqp(c->P, rec, batch, x, w, st, it, z, zc, c->scratch.p, act, s);
+    if (e == hipSuccess) c->order.leave(s);
     return e;
 }
 
@@ -222,11 +171,11 @@ int lmpc_hoqp_create(const lmpc_hoqp_dims* d, int max_batch, int device, lmpc_ho
     fill_dev(c->P, d);
     const size_t rec = (size_t)max_batch * c->P.rec_len, outd = (size_t)max_batch * (c->P.L * c->P.n + c->P.slack_len);
     bool ok = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess &&
-              hipEventCreateWithFlags(&c->ev, hipEventDisableTiming) == hipSuccess &&
+              c->order.create() == hipSuccess &&
               hipMalloc(&c->d_rec, rec * sizeof(double)) == hipSuccess &&
               hipMalloc(&c->d_out, outd * sizeof(double)) == hipSuccess &&
               hipMalloc(&c->d_st, (size_t)max_batch * (1 + c->P.L) * sizeof(int32_t)) == hipSuccess &&
-              ensure_scratch(c, max_batch) == hipSuccess;
+              ensure_scratch(c, max_batch) == LMPC_OK;
     if (!ok) {
         lmpc_hoqp_destroy(c);
         return LMPC_ERR_ALLOC;
@@ -239,16 +188,15 @@ void lmpc_hoqp_destroy(lmpc_hoqp_ctx* c) {
     if (!c) return;
     DeviceScope scope(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->pend && c->last != c->stream) (void)hipDeviceSynchronize();  // its stream may be gone by now
-    else if (c->ev_live) (void)hipEventSynchronize(c->ev);
+    (void)c->order.wait_host(c->stream);  // the last launch on a caller's stream
     (void)hipFree(c->d_rec);
     (void)hipFree(c->d_out);
     (void)hipFree(c->d_st);
-    (void)hipFree(c->d_scratch);
-    (void)hipFree(c->d_z);
-    (void)hipFree(c->d_zc);
-    (void)hipFree(c->d_act);
-    if (c->ev) (void)hipEventDestroy(c->ev);
+    c->scratch.release();
+    c->z.release();
+    c->zc.release();
+    c->act.release();
+    c->order.destroy();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -273,37 +221,24 @@ static int solve_batch_impl(lmpc_hoqp_ctx* c, const double* tasks, int batch, do
     DeviceScope scope(c->device);
     if (!scope.ok) return LMPC_ERR_DEVICE;
     const size_t nx = (size_t)batch * c->P.L * c->P.n, nw = (size_t)batch * c->P.slack_len;
-    const size_t nz = (size_t)c->max_batch * c->P.L * c->P.n * c->P.n;
-    if (z && !c->d_z) {  // staging for the stacked Z matrices, on first use (max_batch x levels x n x n)
-        if (hipMalloc(&c->d_z, nz * sizeof(double)) != hipSuccess ||
-            hipMalloc(&c->d_zc, (size_t)c->max_batch * c->P.L * sizeof(int32_t)) != hipSuccess) {
-            (void)hipFree(c->d_z);
-            c->d_z = nullptr;
-            return LMPC_ERR_ALLOC;
-        }
-    }
+    const size_t nzc = (size_t)c->max_batch * c->P.L;
+    // staging for the stacked Z matrices (max_batch x levels x n x n) and for the active-set blocks, on first use
+    if (z && (c->z.grow(nzc * c->P.n * c->P.n) != LMPC_OK || c->zc.grow(nzc) != LMPC_OK)) return LMPC_ERR_ALLOC;
+    if (act && c->act.grow((size_t)c->max_batch * c->P.act_len) != LMPC_OK) return LMPC_ERR_ALLOC;
     const size_t nact = (size_t)batch * c->P.act_len * sizeof(uint64_t);
-    if (act && !c->d_act && hipMalloc(&c->d_act, (size_t)c->max_batch * c->P.act_len * sizeof(uint64_t)) != hipSuccess) {
-        c->d_act = nullptr;
-        return LMPC_ERR_ALLOC;
-    }
     double* d_x = c->d_out;
     double* d_w = c->d_out + nx;
     int32_t* d_status = c->d_st;
     int32_t* d_iters = c->d_st + batch;
     hipStream_t s = c->stream;
-    // a device-path launch still pending on a caller's stream: wait for the device (that stream may be gone)
-    if (c->pend && c->last != s) {
-        if (hipDeviceSynchronize() != hipSuccess) return LMPC_ERR_DEVICE;
-        c->pend = false;
-        c->ev_live = false;
-    }
+    // a device-path launch may still run on a caller's stream: wait for it on the host (that stream may be gone)
+    if (c->order.wait_host(s) != hipSuccess) return LMPC_ERR_DEVICE;
     if (hipMemcpyAsync(c->d_rec, tasks, (size_t)batch * c->P.rec_len * sizeof(double), hipMemcpyHostToDevice, s) !=
         hipSuccess)
         return LMPC_ERR_DEVICE;
-    if (act && hipMemcpyAsync(c->d_act, act, nact, hipMemcpyHostToDevice, s) != hipSuccess) return LMPC_ERR_DEVICE;
-    if (launch(c, c->d_rec, batch, d_x, d_w, d_status, d_iters, z ? c->d_z : nullptr, z ? c->d_zc : nullptr,
-               act ? c->d_act : nullptr, s) != hipSuccess)
+    if (act && hipMemcpyAsync(c->act.p, act, nact, hipMemcpyHostToDevice, s) != hipSuccess) return LMPC_ERR_DEVICE;
+    if (launch(c, c->d_rec, batch, d_x, d_w, d_status, d_iters, z ? c->z.p : nullptr, z ? c->zc.p : nullptr,
+               act ? c->act.p : nullptr, s) != hipSuccess)
         return LMPC_ERR_LAUNCH;
     bool ok = hipMemcpyAsync(x, d_x, nx * sizeof(double), hipMemcpyDeviceToHost, s) == hipSuccess;
     if (nw) ok = ok && hipMemcpyAsync(slack, d_w, nw * sizeof(double), hipMemcpyDeviceToHost, s) == hipSuccess;
@@ -312,12 +247,12 @@ static int solve_batch_impl(lmpc_hoqp_ctx* c, const double* tasks, int batch, do
         ok = ok && hipMemcpyAsync(iters, d_iters, (size_t)batch * c->P.L * sizeof(int32_t), hipMemcpyDeviceToHost, s) ==
                        hipSuccess;
     if (z)
-        ok = ok && hipMemcpyAsync(z, c->d_z, (size_t)batch * c->P.L * c->P.n * c->P.n * sizeof(double),
+        ok = ok && hipMemcpyAsync(z, c->z.p, (size_t)batch * c->P.L * c->P.n * c->P.n * sizeof(double),
                                   hipMemcpyDeviceToHost, s) == hipSuccess;
     if (z && zcols)
-        ok = ok && hipMemcpyAsync(zcols, c->d_zc, (size_t)batch * c->P.L * sizeof(int32_t), hipMemcpyDeviceToHost, s) ==
+        ok = ok && hipMemcpyAsync(zcols, c->zc.p, (size_t)batch * c->P.L * sizeof(int32_t), hipMemcpyDeviceToHost, s) ==
                        hipSuccess;
-    if (act) ok = ok && hipMemcpyAsync(act, c->d_act, nact, hipMemcpyDeviceToHost, s) == hipSuccess;
+    if (act) ok = ok && hipMemcpyAsync(act, c->act.p, nact, hipMemcpyDeviceToHost, s) == hipSuccess;
     ok = ok && hipStreamSynchronize(s) == hipSuccess;
     return ok ? LMPC_OK : LMPC_ERR_DEVICE;
 }
@@ -379,10 +314,8 @@ int lmpc_hoqp_sync(lmpc_hoqp_ctx* c) {
     if (!c) return LMPC_ERR_ARG;
     DeviceScope scope(c->device);
     if (!scope.ok) return LMPC_ERR_DEVICE;
-    bool ok = hipStreamSynchronize(c->stream) == hipSuccess;
-    if (c->pend && c->last != c->stream) ok = ok && hipDeviceSynchronize() == hipSuccess;
-    else if (c->ev_live) ok = ok && hipEventSynchronize(c->ev) == hipSuccess;
-    return ok ? LMPC_OK : LMPC_ERR_DEVICE;
+    const bool ok = hipStreamSynchronize(c->stream) == hipSuccess;
+    return ok && c->order.wait_host(c->stream) == hipSuccess ? LMPC_OK : LMPC_ERR_DEVICE;
 }
 
 }  // extern "C"

@@ -16,6 +16,12 @@
 #include "lmpc/lmpc_stack.h"
 #include "lmpc_common.h"
 #include "lmpc_device.h"
+#include "lmpc_launch.h"
+
+using lmpc_launch::DeviceBuffer;
+using lmpc_launch::DeviceScope;
+using lmpc_launch::launch_rc;
+using lmpc_launch::stream_ok;
 
 namespace lmpc {
 hipError_t launch_qp(const DevParams& prm, const double* rec, const uint8_t* contact, const double* normals,
@@ -60,29 +66,18 @@ struct lmpc_ctx {
     uint8_t* h_in = nullptr;
     uint8_t* h_out = nullptr;
     int riccati = LMPC_RICCATI_LDS;  // the Riccati kernel of cold solves (lmpc_set_riccati_path)
-    double* d_scratch = nullptr;  // per-QP Riccati factors (L^-1, V, K, P2) of the scratch kernel, grown on demand
-    uint8_t* d_done = nullptr;    // per-QP flag: solved by the dense-path kernel (else the Riccati kernel solves it)
-    size_t scratch_qps = 0;
-    size_t done_qps = 0;
-    double* d_crec = nullptr;     // records expanded from commands (lmpc_solve_commands_device), grown on demand
-    uint8_t* d_ccon = nullptr;
-    size_t cmd_qps = 0;
-    // the rollout's own buffers (lmpc_rollout_device), grown on demand like d_crec: the solves' forces (u_0 is each
-    // QP's first 12) and the shifted active set
-    double* d_rgrf = nullptr;
-    uint8_t* d_ract = nullptr;
-    size_t roll_qps = 0;
-    // Ordering of the context's own buffers (d_scratch, d_done, the staging blocks, d_crec/d_ccon) across
-    // streams: a launch that uses them notes its stream (ctx_leave); the next such launch on another stream
-    // records `ev` on the noted stream then and waits on it (ctx_enter); a host-pointer call, lmpc_sync and
-    // lmpc_destroy wait for the device instead (the noted stream may be gone by then).  Calls on one stream pay
-    // no event: recording one after every launch cost config 2 ~3 us per step (1.8 %, round 6,
-    // profiles/r06/overhead/).
-    hipEvent_t ev = nullptr;
-    hipStream_t ev_stream = nullptr;  // where ev was last recorded
-    bool ev_live = false;
-    hipStream_t last = nullptr;       // stream of the last launch that used the buffers, not yet fenced
-    bool pend = false;
+    // per-QP buffers, grown on demand (capacities in elements)
+    DeviceBuffer<double> scratch;  // Riccati factors (L^-1, V, K, P2) of the scratch kernel
+    DeviceBuffer<uint8_t> done;    // flag: solved by the dense-path kernel (else the Riccati kernel solves it)
+    DeviceBuffer<double> crec;     // records expanded from commands (lmpc_solve_commands_device) and their contacts
+    DeviceBuffer<uint8_t> ccon;
+    // the rollout's own (lmpc_rollout_device): the solves' forces (u_0 is each QP's first 12), the shifted active set
+    DeviceBuffer<double> rgrf;
+    DeviceBuffer<uint8_t> ract;
+    // Order of the launches that use the context's own buffers (the above and the staging blocks) across streams:
+    // each notes its stream (leave) after ordering itself behind the last one (enter); a host-pointer call, lmpc_sync
+    // and lmpc_destroy wait on the host (wait_host).  The rules: lmpc_order.h.
+    lmpc_launch::Order order;
 };
 
 namespace {
@@ -141,156 +136,43 @@ size_t out_bytes(int H, int batch) {  // grf | status | iters | dense-path hand-
     return (size_t)batch * (12 * (size_t)H * sizeof(double) + 2 * sizeof(int32_t) + 1 + 4 * (size_t)H);
 }
 
-// Every entry point runs on the context's device and leaves the caller's current device as it found it.
-struct DeviceScope {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceScope(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) {
-            prev = -1;
-            return;
-        }
-        ok = prev == dev || hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-    DeviceScope(const DeviceScope&) = delete;
-    DeviceScope& operator=(const DeviceScope&) = delete;
-};
-
-// A caller's stream must belong to the context's device (the null stream is the current device's, which
-// DeviceScope has just made the context's).
-bool stream_ok(hipStream_t s, int dev) {
-    if (!s) return true;
-    hipDevice_t d = -1;
-    return hipStreamGetDevice(s, &d) == hipSuccess && d == dev;
-}
-
-// Launches that use the context's buffers are ordered as issued, whatever stream each comes on.  ctx_leave notes
-// the launch's stream; ctx_enter, before a launch on stream s, records the event on a noted launch's stream when s
-// differs (everything issued there so far precedes it) and makes s wait for it.  A launch on the noted stream needs
-// nothing: stream order already holds.
-hipError_t ctx_enter(lmpc_ctx* c, hipStream_t s) {
-    if (c->pend) {
-        if (c->last == s) return hipSuccess;
-        const hipError_t e = hipEventRecord(c->ev, c->last);
-        c->pend = false;
-        c->ev_stream = c->last;
-        c->ev_live = e == hipSuccess;
-        if (e != hipSuccess) return e;
-    }
-    if (c->ev_live && c->ev_stream != s) return hipStreamWaitEvent(s, c->ev, 0);
-    return hipSuccess;
-}
-hipError_t ctx_leave(lmpc_ctx* c, hipStream_t s) {
-    c->last = s;
-    c->pend = true;
-    return hipSuccess;
-}
-// Wait on the host for the last launch that used the context's buffers (its stream may have been destroyed since:
-// the device as a whole, which is rare -- a host-pointer call after device-path calls on another stream, lmpc_sync,
-// lmpc_destroy).
-hipError_t ctx_wait_host(lmpc_ctx* c, hipStream_t s) {
-    if (c->pend && c->last != s) {
-        const hipError_t e = hipDeviceSynchronize();
-        c->pend = false;
-        return e;
-    }
-    if (c->ev_live && c->ev_stream != s) return hipEventSynchronize(c->ev);
-    return hipSuccess;
-}
-
 void free_bufs(lmpc_ctx* c) {
     (void)hipFree(c->d_in);
     (void)hipFree(c->d_out);
     (void)hipHostFree(c->h_in);
     (void)hipHostFree(c->h_out);
-    (void)hipFree(c->d_scratch);
-    (void)hipFree(c->d_done);
-    c->d_scratch = nullptr;
-    c->d_done = nullptr;
-    c->scratch_qps = 0;
-    c->done_qps = 0;
-    (void)hipFree(c->d_crec);
-    (void)hipFree(c->d_ccon);
-    c->d_crec = nullptr;
-    c->d_ccon = nullptr;
-    c->cmd_qps = 0;
-    (void)hipFree(c->d_rgrf);
-    (void)hipFree(c->d_ract);
-    c->d_rgrf = nullptr;
-    c->d_ract = nullptr;
-    c->roll_qps = 0;
     c->d_in = c->d_out = c->h_in = c->h_out = nullptr;
+    c->scratch.release();
+    c->done.release();
+    c->crec.release();
+    c->ccon.release();
+    c->rgrf.release();
+    c->ract.release();
 }
 
 // The per-QP device buffers of a batch: the dense path's hand-over flags (always) and, when the scratch Riccati
-// kernel runs (selected, or a warm start), its factor workspace.  Grown, never shrunk; a buffer in use by a queued
-// launch is waited for before it is freed.
+// kernel runs (selected, or a warm start), its factor workspace.
 int ensure_ws(lmpc_ctx* c, int batch, bool scratch) {
-    const bool grow_done = (size_t)batch > c->done_qps, grow_scr = scratch && (size_t)batch > c->scratch_qps;
-    if (!grow_done && !grow_scr) return LMPC_OK;
+    const size_t nd = (size_t)batch, ns = scratch ? (size_t)batch * lmpc::scratch_doubles_per_qp(c->H) : 0;
+    if (nd <= c->done.cap && ns <= c->scratch.cap) return LMPC_OK;
     DeviceScope ds(c->device);
     if (!ds.ok) return LMPC_ERR_DEVICE;
-    if (c->d_done || c->d_scratch) {
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipDeviceSynchronize();  // queued launches on callers' streams may still read the old buffers
-    }
-    if (grow_done) {
-        (void)hipFree(c->d_done);
-        c->d_done = nullptr;
-        c->done_qps = 0;
-        if (hipMalloc(&c->d_done, (size_t)batch) != hipSuccess) {
-            c->d_done = nullptr;
-            return LMPC_ERR_ALLOC;
-        }
-        c->done_qps = (size_t)batch;
-    }
-    if (grow_scr) {
-        (void)hipFree(c->d_scratch);
-        c->d_scratch = nullptr;
-        c->scratch_qps = 0;
-        if (hipMalloc(&c->d_scratch, (size_t)batch * lmpc::scratch_doubles_per_qp(c->H) * sizeof(double)) != hipSuccess) {
-            c->d_scratch = nullptr;
-            return LMPC_ERR_ALLOC;
-        }
-        c->scratch_qps = (size_t)batch;
-    }
-    return LMPC_OK;
+    const int rc = c->done.grow(nd);
+    return rc != LMPC_OK ? rc : c->scratch.grow(ns);
 }
 
-// The record buffers commands are expanded into (lmpc_solve_commands_device and its warm and rollout forms); the
-// caller has set the context's device.
+// The record buffers commands are expanded into (lmpc_solve_commands_device and its warm and rollout forms), for
+// `batch` QPs; the caller has set the context's device.
 int ensure_cmd(lmpc_ctx* c, int batch) {
-    if ((size_t)batch <= c->cmd_qps) return LMPC_OK;
-    (void)hipDeviceSynchronize();  // the old buffers may still be read by queued work
-    (void)hipFree(c->d_crec);
-    (void)hipFree(c->d_ccon);
-    c->d_crec = nullptr;
-    c->d_ccon = nullptr;
-    c->cmd_qps = 0;
-    if (hipMalloc(&c->d_crec, (size_t)batch * lmpc_record_len(c->H) * sizeof(double)) != hipSuccess ||
-        hipMalloc(&c->d_ccon, (size_t)batch * 4 * c->H) != hipSuccess)
-        return LMPC_ERR_ALLOC;
-    c->cmd_qps = (size_t)batch;
-    return LMPC_OK;
+    const int rc = c->crec.grow((size_t)batch * lmpc_record_len(c->H));
+    return rc != LMPC_OK ? rc : c->ccon.grow((size_t)batch * 4 * c->H);
 }
+size_t cmd_qps(const lmpc_ctx* c) { return c->ccon.cap / (4 * (size_t)c->H); }  // ccon grows last
 
 // The rollout's buffers for `batch` robots.
 int ensure_roll(lmpc_ctx* c, int batch) {
-    if ((size_t)batch <= c->roll_qps) return LMPC_OK;
-    (void)hipDeviceSynchronize();
-    (void)hipFree(c->d_rgrf);
-    (void)hipFree(c->d_ract);
-    c->d_rgrf = nullptr;
-    c->d_ract = nullptr;
-    c->roll_qps = 0;
-    if (hipMalloc(&c->d_rgrf, (size_t)batch * 12 * c->H * sizeof(double)) != hipSuccess ||
-        hipMalloc(&c->d_ract, (size_t)batch * 4 * c->H) != hipSuccess)
-        return LMPC_ERR_ALLOC;
-    c->roll_qps = (size_t)batch;
-    return LMPC_OK;
+    const int rc = c->rgrf.grow((size_t)batch * 12 * c->H);
+    return rc != LMPC_OK ? rc : c->ract.grow((size_t)batch * 4 * c->H);
 }
 
 // The Riccati kernel of a cold solve: the LDS-resident one (lmpc_lq.hip) or the scratch one (lmpc_kernels.hip,
@@ -303,7 +185,7 @@ hipError_t launch_riccati(const lmpc_ctx* c, const lmpc::DevParams& prm, const d
                           const double* nrm, int batch, double* grf, int32_t* st, int32_t* it, const uint8_t* done,
                           hipStream_t s) {
     if (!uses_scratch(c, prm)) return lmpc::launch_lq(prm, rec, con, nrm, batch, grf, st, it, done, s);
-    return lmpc::launch_qp(prm, rec, con, nrm, batch, grf, st, it, c->d_scratch, done, s);
+    return lmpc::launch_qp(prm, rec, con, nrm, batch, grf, st, it, c->scratch.p, done, s);
 }
 
 }  // namespace
@@ -334,13 +216,8 @@ int lmpc_create(const lmpc_params* p, int horizon, int max_batch, int device, lm
     c->prm.dense = horizon > lmpc::DENSE_MAX_H ? 0 : 1;
     if (hipDeviceGetAttribute(&c->prm.cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess)
         c->prm.cus = 256;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete c;
-        return LMPC_ERR_DEVICE;
-    }
-    if (hipEventCreateWithFlags(&c->ev, hipEventDisableTiming) != hipSuccess) {
-        (void)hipStreamDestroy(c->stream);
-        delete c;
+    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess || c->order.create() != hipSuccess) {
+        lmpc_destroy(c);
         return LMPC_ERR_DEVICE;
     }
     if (max_batch > 0) {
@@ -348,20 +225,10 @@ int lmpc_create(const lmpc_params* p, int horizon, int max_batch, int device, lm
         bool ok = hipMalloc(&c->d_in, in_b) == hipSuccess && hipMalloc(&c->d_out, out_b) == hipSuccess &&
                   hipHostMalloc(&c->h_in, in_b, hipHostMallocDefault) == hipSuccess &&
                   hipHostMalloc(&c->h_out, out_b, hipHostMallocDefault) == hipSuccess;
-        if (!ok) {
-            free_bufs(c);
-            (void)hipEventDestroy(c->ev);
-            (void)hipStreamDestroy(c->stream);
-            delete c;
+        if (!ok || ensure_ws(c, max_batch, c->riccati == LMPC_RICCATI_SCRATCH) != LMPC_OK) {
+            lmpc_destroy(c);
             return LMPC_ERR_ALLOC;
         }
-    }
-    if (max_batch > 0 && ensure_ws(c, max_batch, c->riccati == LMPC_RICCATI_SCRATCH) != LMPC_OK) {
-        free_bufs(c);
-        (void)hipEventDestroy(c->ev);
-        (void)hipStreamDestroy(c->stream);
-        delete c;
-        return LMPC_ERR_ALLOC;
     }
     *out = c;
     return LMPC_OK;
@@ -371,9 +238,9 @@ void lmpc_destroy(lmpc_ctx* c) {
     if (!c) return;
     DeviceScope ds(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    (void)ctx_wait_host(c, c->stream);  // the last launch on a caller's stream
+    (void)c->order.wait_host(c->stream);  // the last launch on a caller's stream
     free_bufs(c);
-    if (c->ev) (void)hipEventDestroy(c->ev);
+    c->order.destroy();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -431,7 +298,7 @@ int lmpc_solve_batch_device_ex(lmpc_ctx* c, const double* d_rec, const uint8_t* 
         const int rc = ensure_ws(c, batch, uses_scratch(c, c->prm));
         if (rc != LMPC_OK) return rc;
     }
-    hipError_t e = ctx_enter(c, s);
+    hipError_t e = c->order.enter(s);
     // condensed dense kernel first; it flags the QPs it solved and the Riccati kernel solves the rest
     // (more than 20 stance leg-steps, or a dense QP left without a verified optimum).  At most one QP per SIMD
     // (both kernels one wave per SIMD) the two run as one launch, each QP's Riccati solve after its dense one in
@@ -439,30 +306,27 @@ int lmpc_solve_batch_device_ex(lmpc_ctx* c, const double* d_rec, const uint8_t* 
     bool fused = false;
     if (e == hipSuccess && c->prm.dense == 1 && !uses_scratch(c, c->prm)) {
         const hipError_t f = lmpc::launch_dense_lq(c->prm, d_rec, d_contact, d_normals, batch, d_grf, d_status,
-                                                    d_iters, c->d_done, s);
+                                                    d_iters, c->done.p, s);
         if (f == hipSuccess) fused = true;
         else if (f != hipErrorNotSupported) e = f;
     }
     if (!fused) {
         if (e == hipSuccess && c->prm.dense == 2)
-            e = lmpc::launch_gi(c->prm, d_rec, d_contact, d_normals, batch, d_grf, d_status, d_iters, c->d_done, s);
+            e = lmpc::launch_gi(c->prm, d_rec, d_contact, d_normals, batch, d_grf, d_status, d_iters, c->done.p, s);
         else if (e == hipSuccess && c->prm.dense == 1)
-            e = lmpc::launch_dense(c->prm, d_rec, d_contact, d_normals, batch, d_grf, d_status, d_iters, c->d_done, s);
+            e = lmpc::launch_dense(c->prm, d_rec, d_contact, d_normals, batch, d_grf, d_status, d_iters, c->done.p, s);
         if (e == hipSuccess)
             e = launch_riccati(c, c->prm, d_rec, d_contact, d_normals, batch, d_grf, d_status, d_iters,
-                               c->prm.dense ? c->d_done : nullptr, s);
+                               c->prm.dense ? c->done.p : nullptr, s);
     }
-    if (e == hipSuccess) e = ctx_leave(c, s);
-    if (e == hipErrorInvalidDeviceFunction || e == hipErrorNoBinaryForGpu) return LMPC_ERR_NOT_BUILT;
-    return e == hipSuccess ? LMPC_OK : LMPC_ERR_LAUNCH;
+    if (e == hipSuccess) c->order.leave(s);
+    return launch_rc(e);
 }
 
 int lmpc_solve_batch_device(lmpc_ctx* c, const double* d_rec, const uint8_t* d_contact, int batch, double* d_grf,
                             int32_t* d_status, int32_t* d_iters, void* stream) {
     return lmpc_solve_batch_device_ex(c, d_rec, d_contact, nullptr, batch, d_grf, d_status, d_iters, stream);
 }
-
-static int launch_rc(hipError_t e);
 
 // The host-pointer path: one pinned copy in, the kernels, one pinned copy out.  act_in / act_out (warm start,
 // lmpc_solve_batch_warm): every QP goes to the Riccati kernel, which starts from act_in and reports act_out.
@@ -489,7 +353,7 @@ static int solve_host(lmpc_ctx* c, const double* rec, const uint8_t* contact, co
     const size_t nact = act_in ? ncon : 0;
     // the pinned staging blocks and the factor scratch may still be in use by an earlier asynchronous
     // device-path call on another stream: wait for it before the host writes the staging block
-    if (ctx_wait_host(c, s) != hipSuccess) return LMPC_ERR_DEVICE;
+    if (c->order.wait_host(s) != hipSuccess) return LMPC_ERR_DEVICE;
     std::memcpy(c->h_in, rec, nrec);
     if (normals) std::memcpy(c->h_in + nrec, normals, nnrm);
     std::memcpy(c->h_in + nrec + nnrm, contact, ncon);
@@ -525,7 +389,7 @@ static int solve_host(lmpc_ctx* c, const double* rec, const uint8_t* contact, co
                : lmpc::launch_dense(prm, d_rec, d_con, d_nrm, batch, d_grf, d_st, d_st + batch, d_done, s);
     if (e == hipSuccess && n_ric)
         e = launch_riccati(c, prm, d_rec, d_con, d_nrm, batch, d_grf, d_st, d_st + batch, prm.dense ? d_done : nullptr, s);
-    if (e == hipSuccess) e = ctx_leave(c, s);
+    if (e == hipSuccess) c->order.leave(s);
     if (e != hipSuccess) return launch_rc(e);
     // one copy back: [grf | status | iters], plus the hand-over flags (dense path) or the active set (warm)
     const size_t nout = act_out ? ngrf + 2 * nst + batch + ncon : ngrf + 2 * nst + (n_dense ? (size_t)batch : 0);
@@ -541,7 +405,7 @@ static int solve_host(lmpc_ctx* c, const double* rec, const uint8_t* contact, co
         if (left) {
             if (ensure_ws(c, batch, uses_scratch(c, prm)) != LMPC_OK) return LMPC_ERR_ALLOC;
             e = launch_riccati(c, prm, d_rec, d_con, d_nrm, batch, d_grf, d_st, d_st + batch, d_done, s);
-            if (e == hipSuccess) e = ctx_leave(c, s);
+            if (e == hipSuccess) c->order.leave(s);
             if (e != hipSuccess) return launch_rc(e);
             if (hipMemcpyAsync(c->h_out, c->d_out, ngrf + 2 * nst, hipMemcpyDeviceToHost, s) != hipSuccess ||
                 hipStreamSynchronize(s) != hipSuccess)
@@ -580,11 +444,6 @@ int lmpc_solve_batch(lmpc_ctx* c, const double* rec, const uint8_t* contact, int
     return lmpc_solve_batch_ex(c, rec, contact, nullptr, batch, grf, status, iters);
 }
 
-static int launch_rc(hipError_t e) {
-    if (e == hipErrorInvalidDeviceFunction || e == hipErrorNoBinaryForGpu) return LMPC_ERR_NOT_BUILT;
-    return e == hipSuccess ? LMPC_OK : LMPC_ERR_LAUNCH;
-}
-
 // Entry points that launch on the caller's stream without touching the context's buffers: device scope and
 // stream check only.
 #define LMPC_DEVICE_ENTRY(c, s)                         \
@@ -608,10 +467,10 @@ int lmpc_solve_commands_device(lmpc_ctx* c, const lmpc_command* d_cmd, const dou
     LMPC_DEVICE_ENTRY(c, s);
     if (ensure_cmd(c, batch) != LMPC_OK) return LMPC_ERR_ALLOC;
     // the expansion overwrites the context's record buffers: order it behind the previous solve that read them
-    hipError_t e = ctx_enter(c, s);
-    if (e == hipSuccess) e = lmpc::launch_records(d_cmd, batch, c->H, c->prm.dt, c->d_crec, c->d_ccon, s);
+    hipError_t e = c->order.enter(s);
+    if (e == hipSuccess) e = lmpc::launch_records(d_cmd, batch, c->H, c->prm.dt, c->crec.p, c->ccon.p, s);
     if (e != hipSuccess) return launch_rc(e);
-    return lmpc_solve_batch_device_ex(c, c->d_crec, c->d_ccon, d_normals, batch, d_grf, d_status, d_iters, s);
+    return lmpc_solve_batch_device_ex(c, c->crec.p, c->ccon.p, d_normals, batch, d_grf, d_status, d_iters, s);
 }
 
 int lmpc_synth_commands_device(lmpc_ctx* c, const lmpc_synth_cfg* cfg, uint64_t seed, int64_t first_index, int count,
@@ -658,10 +517,10 @@ static int solve_warm_device(lmpc_ctx* c, const double* d_rec, const uint8_t* d_
     prm.act_out = d_act_out;
     const int rc = ensure_ws(c, batch, true);
     if (rc != LMPC_OK) return rc;
-    hipError_t e = ctx_enter(c, s);
+    hipError_t e = c->order.enter(s);
     if (e == hipSuccess)
-        e = lmpc::launch_qp(prm, d_rec, d_con, d_normals, batch, d_grf, d_status, d_iters, c->d_scratch, nullptr, s);
-    if (e == hipSuccess) e = ctx_leave(c, s);
+        e = lmpc::launch_qp(prm, d_rec, d_con, d_normals, batch, d_grf, d_status, d_iters, c->scratch.p, nullptr, s);
+    if (e == hipSuccess) c->order.leave(s);
     return launch_rc(e);
 }
 
@@ -672,10 +531,10 @@ int lmpc_solve_commands_warm_device(lmpc_ctx* c, const lmpc_command* d_cmd, cons
     if (batch == 0) return LMPC_OK;
     LMPC_DEVICE_ENTRY(c, s);
     if (ensure_cmd(c, batch) != LMPC_OK) return LMPC_ERR_ALLOC;
-    hipError_t e = ctx_enter(c, s);
-    if (e == hipSuccess) e = lmpc::launch_records(d_cmd, batch, c->H, c->prm.dt, c->d_crec, c->d_ccon, s);
+    hipError_t e = c->order.enter(s);
+    if (e == hipSuccess) e = lmpc::launch_records(d_cmd, batch, c->H, c->prm.dt, c->crec.p, c->ccon.p, s);
     if (e != hipSuccess) return launch_rc(e);
-    return solve_warm_device(c, c->d_crec, c->d_ccon, d_normals, batch, d_act_in, d_act_out, d_grf, d_status, d_iters, s);
+    return solve_warm_device(c, c->crec.p, c->ccon.p, d_normals, batch, d_act_in, d_act_out, d_grf, d_status, d_iters, s);
 }
 
 int lmpc_rollout_device(lmpc_ctx* c, const lmpc_rollout_cfg* cfg, lmpc_robot* d_robots, uint8_t* d_act, int batch,
@@ -698,29 +557,29 @@ int lmpc_rollout_device(lmpc_ctx* c, const lmpc_rollout_cfg* cfg, lmpc_robot* d_
     const lmpc_rollout_log& lg = log ? *log : no_log;
     const size_t B = (size_t)batch;
     // the rollout's buffers are the context's: order the first launch behind whatever used them last
-    hipError_t e = ctx_enter(c, s);
+    hipError_t e = c->order.enter(s);
     if (e != hipSuccess) return launch_rc(e);
     for (int t = 0; t <= ticks; ++t) {
         const bool last = t == ticks;
         // the advance launch also expands tick t's commands into the context's record buffers
-        e = lmpc::launch_advance(pp, *cfg, d_robots, batch, t > 0 ? c->d_rgrf : nullptr, c->H, last ? 0 : 1,
+        e = lmpc::launch_advance(pp, *cfg, d_robots, batch, t > 0 ? c->rgrf.p : nullptr, c->H, last ? 0 : 1,
                                  !last && lg.cmd ? lg.cmd + (size_t)t * B : nullptr,
                                  t > 0 && lg.u0 ? lg.u0 + (size_t)(t - 1) * B * 12 : nullptr,
-                                 t > 0 && lg.x ? lg.x + (size_t)(t - 1) * B * 12 : nullptr, c->d_crec, c->d_ccon, s);
+                                 t > 0 && lg.x ? lg.x + (size_t)(t - 1) * B * 12 : nullptr, c->crec.p, c->ccon.p, s);
         if (e != hipSuccess || last) break;
         int32_t* st = lg.status ? lg.status + (size_t)t * B : nullptr;
         int32_t* it = lg.iters ? lg.iters + (size_t)t * B : nullptr;
         int rc;
         if (d_act) {
-            e = lmpc::launch_shift(d_act, batch, c->H, c->d_ract, s);
+            e = lmpc::launch_shift(d_act, batch, c->H, c->ract.p, s);
             if (e != hipSuccess) break;
-            rc = solve_warm_device(c, c->d_crec, c->d_ccon, nullptr, batch, c->d_ract, d_act, c->d_rgrf, st, it, s);
+            rc = solve_warm_device(c, c->crec.p, c->ccon.p, nullptr, batch, c->ract.p, d_act, c->rgrf.p, st, it, s);
         } else {
-            rc = lmpc_solve_batch_device_ex(c, c->d_crec, c->d_ccon, nullptr, batch, c->d_rgrf, st, it, s);
+            rc = lmpc_solve_batch_device_ex(c, c->crec.p, c->ccon.p, nullptr, batch, c->rgrf.p, st, it, s);
         }
         if (rc != LMPC_OK) return rc;
     }
-    if (e == hipSuccess) e = ctx_leave(c, s);
+    if (e == hipSuccess) c->order.leave(s);
     return launch_rc(e);
 }
 
@@ -741,29 +600,29 @@ int lmpc_stack_advance_device(lmpc_ctx* c, const lmpc_rollout_cfg* cfg, lmpc_sta
     if (batch == 0) return LMPC_OK;
     if (ensure_cmd(c, batch) != LMPC_OK) return LMPC_ERR_ALLOC;
     // the expansion overwrites the context's record buffers: order it behind the previous solve that read them
-    hipError_t e = ctx_enter(c, s);
+    hipError_t e = c->order.enter(s);
     if (e == hipSuccess)
-        e = lmpc::launch_stack_advance(c->prm.dt, *cfg, d_robots, d_state, d_sim_out, batch, c->H, c->d_crec, c->d_ccon, s);
-    if (e == hipSuccess) e = ctx_leave(c, s);
+        e = lmpc::launch_stack_advance(c->prm.dt, *cfg, d_robots, d_state, d_sim_out, batch, c->H, c->crec.p, c->ccon.p, s);
+    if (e == hipSuccess) c->order.leave(s);
     return launch_rc(e);
 }
 
 int lmpc_stack_solve_device(lmpc_ctx* c, int batch, double* d_grf, int32_t* d_status, int32_t* d_iters, void* stream) {
-    if (!c || batch < 0 || (size_t)batch > c->cmd_qps || (batch > 0 && !d_grf)) return LMPC_ERR_ARG;
+    if (!c || batch < 0 || (size_t)batch > cmd_qps(c) || (batch > 0 && !d_grf)) return LMPC_ERR_ARG;
     if (batch == 0) return LMPC_OK;
-    return lmpc_solve_batch_device_ex(c, c->d_crec, c->d_ccon, nullptr, batch, d_grf, d_status, d_iters, stream);
+    return lmpc_solve_batch_device_ex(c, c->crec.p, c->ccon.p, nullptr, batch, d_grf, d_status, d_iters, stream);
 }
 
 int lmpc_stack_copy_records_device(lmpc_ctx* c, int batch, double* d_rec, uint8_t* d_contact, void* stream) {
-    if (!c || batch < 0 || (size_t)batch > c->cmd_qps || (batch > 0 && (!d_rec || !d_contact))) return LMPC_ERR_ARG;
+    if (!c || batch < 0 || (size_t)batch > cmd_qps(c) || (batch > 0 && (!d_rec || !d_contact))) return LMPC_ERR_ARG;
     LMPC_DEVICE_ENTRY(c, s);
     if (batch == 0) return LMPC_OK;
-    hipError_t e = ctx_enter(c, s);
+    hipError_t e = c->order.enter(s);
     if (e == hipSuccess)
-        e = hipMemcpyAsync(d_rec, c->d_crec, (size_t)batch * lmpc_record_len(c->H) * sizeof(double),
+        e = hipMemcpyAsync(d_rec, c->crec.p, (size_t)batch * lmpc_record_len(c->H) * sizeof(double),
                            hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_contact, c->d_ccon, (size_t)batch * 4 * c->H, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = ctx_leave(c, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_contact, c->ccon.p, (size_t)batch * 4 * c->H, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) c->order.leave(s);
     return e == hipSuccess ? LMPC_OK : LMPC_ERR_DEVICE;
 }
 #undef LMPC_DEVICE_ENTRY
@@ -774,7 +633,7 @@ int lmpc_sync(lmpc_ctx* c) {
     if (!ds.ok) return LMPC_ERR_DEVICE;
     if (hipStreamSynchronize(c->stream) != hipSuccess) return LMPC_ERR_DEVICE;
     // and the last launch that used the context's buffers, whatever stream it ran on
-    return ctx_wait_host(c, c->stream) == hipSuccess ? LMPC_OK : LMPC_ERR_DEVICE;
+    return c->order.wait_host(c->stream) == hipSuccess ? LMPC_OK : LMPC_ERR_DEVICE;
 }
 
 }  // extern "C"

@@ -241,6 +241,101 @@ def test_two_streams_of_one_context_are_ordered(hq):
     solver.close()
 
 
+@pytest.fixture(scope="module")
+def alone(hq):
+    """The tick pairs' records solved alone, each by a context of its own that does nothing else: tick A, tick B, and
+    tick B twice over (24 chains).  (dims, x, w, status, iters) per key; the ordering tests hold every result to these
+    bits."""
+    g = pairs()
+    dims = dims_from(g["dims"])
+    out = {}
+    for key, rec in (("a", g["rec_a"]), ("b", g["rec_b"]), ("bb", np.concatenate([g["rec_b"], g["rec_b"]]))):
+        solver = hq.HoqpBatch(dims, rec.shape[0])
+        out[key] = tuple(solver.solve(rec))
+        solver.close()
+    return dims, out
+
+
+def device_outputs(torch, B):
+    return (torch.zeros((B, 3, 42), dtype=torch.float64, device="cuda"), torch.zeros((B, 44), dtype=torch.float64, device="cuda"),
+            torch.zeros(B, dtype=torch.int32, device="cuda"), torch.zeros((B, 3), dtype=torch.int32, device="cuda"))
+
+
+def same_bits(outs, ref):
+    return all(np.array_equal(o.cpu().numpy() if hasattr(o, "cpu") else o, r) for o, r in zip(outs, ref))
+
+
+def test_stream_gone_before_the_next_call(hq, alone):
+    """test_gpu_parity.py's test of the same name, for the hierarchical QP's context: a device-path solve on a caller's
+    stream A leaves nothing recorded on A.  With A destroyed right after the call (its solve may still run), the next
+    host-pointer solve, lmpc_hoqp_sync and lmpc_hoqp_destroy wait for the device instead of touching A: no crash, and
+    every result equals the same solve run alone."""
+    import ctypes
+
+    import torch
+
+    hip = ctypes.CDLL("libamdhip64.so")
+    hip.hipStreamCreateWithFlags.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint]
+    hip.hipStreamDestroy.argtypes = [ctypes.c_void_p]
+    g = pairs()
+    dims, ref = alone
+    d_a = torch.from_numpy(g["rec_a"]).cuda()
+    for after in ("host", "sync", "close"):
+        t = hq.HoqpBatch(dims, 12)
+        a = ctypes.c_void_p()
+        assert hip.hipStreamCreateWithFlags(ctypes.byref(a), 1) == 0  # hipStreamNonBlocking
+        outs = device_outputs(torch, 12)
+        torch.cuda.synchronize()
+        t.solve_device(d_a, *outs, stream=torch.cuda.ExternalStream(a.value))  # returns at once
+        assert hip.hipStreamDestroy(a) == 0                                     # the caller's stream is gone
+        if after == "host":
+            assert same_bits(t.solve(g["rec_b"]), ref["b"])  # waits for the device, never for A
+        elif after == "sync":
+            assert t._L.lmpc_hoqp_sync(t._ctx) == 0
+        t.close()
+        torch.cuda.synchronize()
+        assert same_bits(outs, ref["a"]), after
+
+
+def test_scratch_growth_with_a_launch_pending(hq, alone):
+    """A context made for 12 chains: 12 on stream A, then 24 on stream B.  The second call grows the scratch, and the
+    old block is the one the first launch may still be working in: both results equal the solves run alone."""
+    import torch
+
+    g = pairs()
+    dims, ref = alone
+    solver = hq.HoqpBatch(dims, 12)
+    sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+    d_a = torch.from_numpy(g["rec_a"]).cuda()
+    d_bb = torch.from_numpy(np.concatenate([g["rec_b"], g["rec_b"]])).cuda()
+    o1, o2 = device_outputs(torch, 12), device_outputs(torch, 24)
+    torch.cuda.synchronize()
+    solver.solve_device(d_a, *o1, stream=sa)
+    solver.solve_device(d_bb, *o2, stream=sb)
+    torch.cuda.synchronize()
+    assert same_bits(o1, ref["a"]) and same_bits(o2, ref["bb"])
+    solver.close()
+
+
+def test_host_path_behind_a_device_call_on_another_stream(hq, alone):
+    """A device-path solve on a caller's stream, then at once a host-pointer solve (the context's own stream): they
+    share the scratch, so the second waits for the first; both results equal the solves run alone."""
+    import torch
+
+    g = pairs()
+    dims, ref = alone
+    solver = hq.HoqpBatch(dims, 12)
+    sa = torch.cuda.Stream()
+    d_a = torch.from_numpy(g["rec_a"]).cuda()
+    o1 = device_outputs(torch, 12)
+    torch.cuda.synchronize()
+    solver.solve_device(d_a, *o1, stream=sa)
+    assert same_bits(solver.solve(g["rec_b"]), ref["b"])
+    torch.cuda.synchronize()
+    assert same_bits(o1, ref["a"])
+    solver.close()
+
+
 def test_closed_loop_wbc_sim(hq):
     """WbcSim(warm=True), 4 standing Go1 robots, 10 ticks: every tick re-solved cold from the logged state."""
     import torch

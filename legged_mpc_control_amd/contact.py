@@ -20,11 +20,11 @@ import ctypes
 
 import numpy as np
 
+from . import _device as D
 from . import _native as N
-from .hoqp import check_device_tensor
-from .rbd import STATE_BYTES, _batch_device
+from .rbd import STATE_BYTES
 from .sim import OUT_BYTES as SIM_OUT_BYTES
-from .sim import _check_rows, _tau_contact
+from .sim import _tau_contact
 
 CFG_BYTES = ctypes.sizeof(N.LmpcContactCfg)  # 72
 OUT_BYTES = ctypes.sizeof(N.LmpcContactOut)  # 176
@@ -93,21 +93,15 @@ def solve_device(c: N.LmpcContactCfg, d_K, d_c, d_mask, d_P, d_out=None, stream=
     d_mask int32 [B][4], d_P float64 [B][12], d_out uint8 [B][176] or None; all contiguous."""
     import torch
 
-    if d_K is None or not getattr(d_K, "is_cuda", False) or d_K.dim() != 2:
-        raise ValueError("d_K: expected a device tensor [B][144]")
-    B, dev = int(d_K.shape[0]), d_K.device
-    check_device_tensor("d_K", d_K, torch.float64, (B, 144), dev)
-    check_device_tensor("d_c", d_c, torch.float64, (B, 12), dev)
-    check_device_tensor("d_mask", d_mask, torch.int32, (B, 4), dev)
-    check_device_tensor("d_P", d_P, torch.float64, (B, 12), dev)
-    if d_out is not None:
-        check_device_tensor("d_out", d_out, torch.uint8, (B, OUT_BYTES), dev)
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
-    N.check(N.lib().lmpc_contact_solve_device(
-        ctypes.byref(c), ctypes.c_void_p(d_K.data_ptr()), ctypes.c_void_p(d_c.data_ptr()),
-        ctypes.c_void_p(d_mask.data_ptr()), B, ctypes.c_void_p(d_P.data_ptr()),
-        ctypes.c_void_p(d_out.data_ptr() if d_out is not None else None), ctypes.c_void_p(s.cuda_stream)),
-        "lmpc_contact_solve_device")
+    B, dev = D.batch("d_K", d_K)
+    D.check("d_K", d_K, torch.float64, (B, 144), dev)
+    D.check("d_c", d_c, torch.float64, (B, 12), dev)
+    D.check("d_mask", d_mask, torch.int32, (B, 4), dev)
+    D.check("d_P", d_P, torch.float64, (B, 12), dev)
+    D.check("d_out", d_out, torch.uint8, (B, OUT_BYTES), dev, optional=True)
+    N.check(N.lib().lmpc_contact_solve_device(ctypes.byref(c), d_K.data_ptr(), d_c.data_ptr(), d_mask.data_ptr(), B,
+                                              d_P.data_ptr(), D.ptr(d_out), D.stream(stream, dev)),
+            "lmpc_contact_solve_device")
 
 
 def work_bytes(batch: int) -> int:
@@ -124,25 +118,20 @@ def step_device(model, c: N.LmpcContactCfg, d_state, d_tau, d_mask, d_next, d_ou
     gives the same bits."""
     import torch
 
-    B, dev = _batch_device(d_state)
-    check_device_tensor("d_state", d_state, torch.uint8, (B, STATE_BYTES), dev)
-    ts = _check_rows("d_tau", d_tau, torch.float64, B, 12, dev)
-    ms = _check_rows("d_mask", d_mask, torch.int32, B, 4, dev)
-    check_device_tensor("d_next", d_next, torch.uint8, (B, STATE_BYTES), dev)
-    if d_out is not None:
-        check_device_tensor("d_out", d_out, torch.uint8, (B, SIM_OUT_BYTES), dev)
-    if d_cout is not None:
-        check_device_tensor("d_cout", d_cout, torch.uint8, (B, OUT_BYTES), dev)
-    if d_work is not None:
-        if not getattr(d_work, "is_cuda", False) or d_work.device != dev or d_work.dtype != torch.uint8 or \
-                d_work.dim() != 1 or not d_work.is_contiguous() or d_work.numel() < work_bytes(B):
-            raise ValueError(f"d_work: expected a contiguous uint8 device tensor of at least {work_bytes(B)} bytes")
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    B, dev = D.batch("d_state", d_state)
+    D.check("d_state", d_state, torch.uint8, (B, STATE_BYTES), dev)
+    ts = D.view("d_tau", d_tau, torch.float64, B, 12, dev)
+    ms = D.view("d_mask", d_mask, torch.int32, B, 4, dev)
+    D.check("d_next", d_next, torch.uint8, (B, STATE_BYTES), dev)
+    D.check("d_out", d_out, torch.uint8, (B, SIM_OUT_BYTES), dev, optional=True)
+    D.check("d_cout", d_cout, torch.uint8, (B, OUT_BYTES), dev, optional=True)
+    work = 0
+    if d_work is not None:  # any length from work_bytes(B) up
+        work, _ = D.batch("d_work", d_work)
+        D.check("d_work", d_work, torch.uint8, (work,), dev)
+        if work < work_bytes(B):
+            raise ValueError(f"d_work: {work} bytes, {B} robots need {work_bytes(B)}")
     N.check(N.lib().lmpc_contact_step_device(
-        ctypes.byref(model), ctypes.byref(c), ctypes.c_void_p(d_state.data_ptr()), ctypes.c_void_p(d_tau.data_ptr()), ts,
-        ctypes.c_void_p(d_mask.data_ptr()), ms, B, int(substeps), ctypes.c_void_p(d_next.data_ptr()),
-        ctypes.c_void_p(d_out.data_ptr() if d_out is not None else None),
-        ctypes.c_void_p(d_cout.data_ptr() if d_cout is not None else None),
-        ctypes.c_void_p(d_work.data_ptr() if d_work is not None else None), d_work.numel() if d_work is not None else 0,
-        ctypes.c_void_p(s.cuda_stream)),
+        ctypes.byref(model), ctypes.byref(c), d_state.data_ptr(), d_tau.data_ptr(), ts, d_mask.data_ptr(), ms, B,
+        int(substeps), d_next.data_ptr(), D.ptr(d_out), D.ptr(d_cout), D.ptr(d_work), work, D.stream(stream, dev)),
         "lmpc_contact_step_device")

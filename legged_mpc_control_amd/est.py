@@ -22,8 +22,8 @@ import ctypes
 
 import numpy as np
 
+from . import _device as D
 from . import _native as N
-from .hoqp import check_device_tensor
 from .rbd import STATE_BYTES
 from .sim import OUT_BYTES as SIM_OUT_BYTES
 
@@ -125,45 +125,18 @@ def filter_view(buf) -> np.ndarray:
     """uint8 [..., 2744] (torch or NumPy) or an LmpcEstFilter -> structured array with x, P [18, 18], inited, ticks."""
     if isinstance(buf, N.LmpcEstFilter):
         return np.frombuffer(bytes(buf), dtype=FILTER_DTYPE)[0]
-    a = buf.cpu().numpy() if hasattr(buf, "cpu") else np.asarray(buf)
-    return np.ascontiguousarray(a, dtype=np.uint8).view(FILTER_DTYPE)[..., 0]
+    return D.host_view(buf, FILTER_DTYPE)
 
 
 def sensors_view(buf) -> np.ndarray:
-    a = buf.cpu().numpy() if hasattr(buf, "cpu") else np.asarray(buf)
-    return np.ascontiguousarray(a, dtype=np.uint8).view(SENSORS_DTYPE)[..., 0]
+    return D.host_view(buf, SENSORS_DTYPE)
 
 
 def out_view(buf) -> np.ndarray:
-    a = buf.cpu().numpy() if hasattr(buf, "cpu") else np.asarray(buf)
-    return np.ascontiguousarray(a, dtype=np.uint8).view(OUT_DTYPE)[..., 0]
+    return D.host_view(buf, OUT_DTYPE)
 
 
 # ---- device ----------------------------------------------------------------------------------------------------------
-def _batch_dev(t, name):
-    if t is None or not getattr(t, "is_cuda", False) or t.dim() < 1:
-        raise ValueError(f"{name}: expected a device tensor")
-    return int(t.shape[0]), t.device
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else None)
-
-
-def _stream(stream, dev):
-    import torch
-
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
-    return ctypes.c_void_p(s.cuda_stream)
-
-
-def _optional(name, t, width, B, dev):
-    import torch
-
-    if t is not None:
-        check_device_tensor(name, t, torch.uint8, (B, width), dev)
-
-
 def sensors_from_plant_device(model, c: N.LmpcEstCfg, d_state, d_sim_out, d_sensors, tick: int = 0, index0: int = 0,
                               d_gait=None, stream=None):
     """A batch of sensor readings on the device (lmpc_est_sensors_from_plant_device): d_state uint8 [B][288], d_sim_out
@@ -171,21 +144,16 @@ def sensors_from_plant_device(model, c: N.LmpcEstCfg, d_state, d_sim_out, d_sens
     with any stride, e.g. `gait_view(d_robots)`), LMPC_GAIT_STAND there sets every contact flag."""
     import torch
 
-    B, dev = _batch_dev(d_state, "d_state")
-    check_device_tensor("d_state", d_state, torch.uint8, (B, STATE_BYTES), dev)
-    check_device_tensor("d_sim_out", d_sim_out, torch.uint8, (B, SIM_OUT_BYTES), dev)
-    check_device_tensor("d_sensors", d_sensors, torch.uint8, (B, SENSORS_BYTES), dev)
-    gs = 0
-    if d_gait is not None:
-        if not getattr(d_gait, "is_cuda", False) or d_gait.device != dev or d_gait.dtype != torch.int32 or \
-                tuple(d_gait.shape) != (B,) or (B > 1 and d_gait.stride(0) < 1):
-            raise ValueError("d_gait: expected an int32 device tensor [B] on the states' device")
-        gs = int(d_gait.stride(0)) if B > 1 else 1
+    B, dev = D.batch("d_state", d_state)
+    D.check("d_state", d_state, torch.uint8, (B, STATE_BYTES), dev)
+    D.check("d_sim_out", d_sim_out, torch.uint8, (B, SIM_OUT_BYTES), dev)
+    D.check("d_sensors", d_sensors, torch.uint8, (B, SENSORS_BYTES), dev)
+    gs = D.view("d_gait", d_gait, torch.int32, B, None, dev, optional=True)
     if not 0 <= int(tick) < 2 ** 32:
         raise ValueError("tick outside 0..2^32 - 1")
     N.check(N.lib().lmpc_est_sensors_from_plant_device(
-        ctypes.byref(model), ctypes.byref(c), _ptr(d_state), _ptr(d_sim_out), B, int(index0), int(tick), _ptr(d_gait), gs,
-        _ptr(d_sensors), _stream(stream, dev)), "lmpc_est_sensors_from_plant_device")
+        ctypes.byref(model), ctypes.byref(c), d_state.data_ptr(), d_sim_out.data_ptr(), B, int(index0), int(tick),
+        D.ptr(d_gait), gs, d_sensors.data_ptr(), D.stream(stream, dev)), "lmpc_est_sensors_from_plant_device")
 
 
 def gait_view(d_robots):
@@ -202,24 +170,28 @@ def init_device(model, c: N.LmpcEstCfg, d_sensors, d_filter, d_pos0=None, d_stat
     report into d_state_est uint8 [B][288], d_out uint8 [B][312] and the shadow of d_sim_out into d_shadow."""
     import torch
 
-    B, dev = _batch_dev(d_sensors, "d_sensors")
-    check_device_tensor("d_sensors", d_sensors, torch.uint8, (B, SENSORS_BYTES), dev)
-    check_device_tensor("d_filter", d_filter, torch.uint8, (B, FILTER_BYTES), dev)
-    _optional("d_state_est", d_state_est, STATE_BYTES, B, dev)
-    _optional("d_out", d_out, OUT_BYTES, B, dev)
-    _optional("d_sim_out", d_sim_out, SIM_OUT_BYTES, B, dev)
-    _optional("d_shadow", d_shadow, SIM_OUT_BYTES, B, dev)
+    B, dev = _filter_args(d_sensors, d_filter, d_state_est, d_out, d_sim_out, d_shadow)
+    ps = D.view("d_pos0", d_pos0, torch.float64, B, 3, dev, optional=True)
+    ptr = D.ptr
+    N.check(N.lib().lmpc_est_init_device(
+        ctypes.byref(model), ctypes.byref(c), ptr(d_sensors), ptr(d_pos0), ps, B, ptr(d_filter), ptr(d_state_est),
+        ptr(d_out), ptr(d_sim_out), ptr(d_shadow), D.stream(stream, dev)), "lmpc_est_init_device")
+
+
+def _filter_args(d_sensors, d_filter, d_state_est, d_out, d_sim_out, d_shadow):
+    """The checks init_device and update_device share -> (B, device)."""
+    import torch
+
+    B, dev = D.batch("d_sensors", d_sensors)
+    D.check("d_sensors", d_sensors, torch.uint8, (B, SENSORS_BYTES), dev)
+    D.check("d_filter", d_filter, torch.uint8, (B, FILTER_BYTES), dev)
+    D.check("d_state_est", d_state_est, torch.uint8, (B, STATE_BYTES), dev, optional=True)
+    D.check("d_out", d_out, torch.uint8, (B, OUT_BYTES), dev, optional=True)
+    D.check("d_sim_out", d_sim_out, torch.uint8, (B, SIM_OUT_BYTES), dev, optional=True)
+    D.check("d_shadow", d_shadow, torch.uint8, (B, SIM_OUT_BYTES), dev, optional=True)
     if d_shadow is not None and d_sim_out is None:
         raise ValueError("d_shadow needs d_sim_out")
-    ps = 0
-    if d_pos0 is not None:
-        if not getattr(d_pos0, "is_cuda", False) or d_pos0.device != dev or d_pos0.dtype != torch.float64 or \
-                tuple(d_pos0.shape) != (B, 3) or d_pos0.stride(1) != 1 or (B > 1 and d_pos0.stride(0) < 3):
-            raise ValueError("d_pos0: expected a float64 device tensor [B][3] with unit stride within a row")
-        ps = int(d_pos0.stride(0)) if B > 1 else 3
-    N.check(N.lib().lmpc_est_init_device(
-        ctypes.byref(model), ctypes.byref(c), _ptr(d_sensors), _ptr(d_pos0), ps, B, _ptr(d_filter), _ptr(d_state_est),
-        _ptr(d_out), _ptr(d_sim_out), _ptr(d_shadow), _stream(stream, dev)), "lmpc_est_init_device")
+    return B, dev
 
 
 def update_device(model, c: N.LmpcEstCfg, d_sensors, d_filter, d_state_est=None, d_out=None, d_sim_out=None,
@@ -227,17 +199,10 @@ def update_device(model, c: N.LmpcEstCfg, d_sensors, d_filter, d_state_est=None,
     """One filter update of every robot on the device (lmpc_est_update_device): d_filter in place; d_state_est uint8
     [B][288] and d_out uint8 [B][312] may be None; with d_shadow (uint8 [B][472], not d_sim_out itself) the same launch
     writes the plant's d_sim_out with the estimate's feet and contact flags."""
-    import torch
-
-    B, dev = _batch_dev(d_sensors, "d_sensors")
-    check_device_tensor("d_sensors", d_sensors, torch.uint8, (B, SENSORS_BYTES), dev)
-    check_device_tensor("d_filter", d_filter, torch.uint8, (B, FILTER_BYTES), dev)
-    _optional("d_state_est", d_state_est, STATE_BYTES, B, dev)
-    _optional("d_out", d_out, OUT_BYTES, B, dev)
-    _optional("d_sim_out", d_sim_out, SIM_OUT_BYTES, B, dev)
-    _optional("d_shadow", d_shadow, SIM_OUT_BYTES, B, dev)
-    if d_shadow is not None and (d_sim_out is None or d_shadow.data_ptr() == d_sim_out.data_ptr()):
-        raise ValueError("d_shadow needs d_sim_out and must not alias it")
+    B, dev = _filter_args(d_sensors, d_filter, d_state_est, d_out, d_sim_out, d_shadow)
+    if d_shadow is not None and d_shadow.data_ptr() == d_sim_out.data_ptr():
+        raise ValueError("d_shadow must not alias d_sim_out")
+    ptr = D.ptr
     N.check(N.lib().lmpc_est_update_device(
-        ctypes.byref(model), ctypes.byref(c), _ptr(d_sensors), B, _ptr(d_filter), _ptr(d_state_est), _ptr(d_out),
-        _ptr(d_sim_out), _ptr(d_shadow), _stream(stream, dev)), "lmpc_est_update_device")
+        ctypes.byref(model), ctypes.byref(c), ptr(d_sensors), B, ptr(d_filter), ptr(d_state_est), ptr(d_out),
+        ptr(d_sim_out), ptr(d_shadow), D.stream(stream, dev)), "lmpc_est_update_device")

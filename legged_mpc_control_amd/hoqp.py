@@ -20,6 +20,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
+from . import _device as D
 from . import _native as N
 
 
@@ -193,52 +194,31 @@ class HoqpBatch:
         written in place; not together with d_z."""
         import torch
 
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        B = int(d_rec.shape[0]) if d_rec.dim() >= 1 else -1
-        dev = torch.device("cuda", self.device)
-        check_device_tensor("d_rec", d_rec, torch.float64, (B, self.rec_len), dev)
-        check_device_tensor("d_x", d_x, torch.float64, (B, self.levels, self.n), dev)
-        check_device_tensor("d_w", d_w, torch.float64, (B, max(self.slack_len, 1)), dev, allow_shape=(B, self.slack_len))
-        if d_status is not None:
-            check_device_tensor("d_status", d_status, torch.int32, (B,), dev)
-        if d_iters is not None:
-            check_device_tensor("d_iters", d_iters, torch.int32, (B, self.levels), dev)
-        if d_z is not None:
-            check_device_tensor("d_z", d_z, torch.float64, (B, self.levels, self.n, self.n), dev)
-        if d_zcols is not None:
-            if d_z is None:
-                raise ValueError("d_zcols needs d_z")
-            check_device_tensor("d_zcols", d_zcols, torch.int32, (B, self.levels), dev)
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        B, dev = D.batch("d_rec", d_rec, device=self.device)
+        D.check("d_rec", d_rec, torch.float64, (B, self.rec_len), dev)
+        D.check("d_x", d_x, torch.float64, (B, self.levels, self.n), dev)
+        D.check("d_w", d_w, torch.float64, (B, max(self.slack_len, 1)), dev, allow_shape=(B, self.slack_len))
+        D.check("d_status", d_status, torch.int32, (B,), dev, optional=True)
+        D.check("d_iters", d_iters, torch.int32, (B, self.levels), dev, optional=True)
+        D.check("d_z", d_z, torch.float64, (B, self.levels, self.n, self.n), dev, optional=True)
+        D.check("d_zcols", d_zcols, torch.int32, (B, self.levels), dev, optional=True)
+        if d_zcols is not None and d_z is None:
+            raise ValueError("d_zcols needs d_z")
+        s, ptr = D.stream(stream, dev), D.ptr
         if d_act is not None:
             if d_z is not None:
                 raise ValueError("the warm solve returns no stacked Z matrices (d_act with d_z)")
-            check_device_tensor("d_act", d_act, torch.int64, (B, self.act_len), dev)
+            D.check("d_act", d_act, torch.int64, (B, self.act_len), dev)
             with self._lock:
                 N.check(self._L.lmpc_hoqp_solve_device_warm(self._ctx, ptr(d_rec), B, ptr(d_x), ptr(d_w), ptr(d_status),
-                                                            ptr(d_iters), ptr(d_act), ctypes.c_void_p(s.cuda_stream)),
-                        "lmpc_hoqp_solve_device_warm")
+                                                            ptr(d_iters), ptr(d_act), s), "lmpc_hoqp_solve_device_warm")
             return
         with self._lock:
             N.check(self._L.lmpc_hoqp_solve_device_z(self._ctx, ptr(d_rec), B, ptr(d_x), ptr(d_w), ptr(d_status),
-                                                     ptr(d_iters), ptr(d_z), ptr(d_zcols),
-                                                     ctypes.c_void_p(s.cuda_stream)),
-                    "lmpc_hoqp_solve_device_z")
+                                                     ptr(d_iters), ptr(d_z), ptr(d_zcols), s), "lmpc_hoqp_solve_device_z")
 
 
-def check_device_tensor(name, t, dtype, shape, device, allow_shape=None):
-    """A raw pointer handed to the device path must be a contiguous tensor of this dtype and shape on the
-    context's device: anything else turns into out-of-bounds device writes or wrong results."""
-    if t is None or not hasattr(t, "is_cuda") or not t.is_cuda:
-        raise ValueError(f"{name}: expected a device tensor")
-    if t.device != device:
-        raise ValueError(f"{name}: on {t.device}, the context is on {device}")
-    if t.dtype != dtype:
-        raise ValueError(f"{name}: dtype {t.dtype}, expected {dtype}")
-    if not t.is_contiguous():
-        raise ValueError(f"{name}: must be contiguous")
-    if tuple(t.shape) != tuple(shape) and (allow_shape is None or tuple(t.shape) != tuple(allow_shape)):
-        raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+check_device_tensor = D.check  # the name this check was first published under
 
 
 _batches = {}

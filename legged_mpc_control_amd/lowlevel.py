@@ -20,8 +20,8 @@ import ctypes
 
 import numpy as np
 
+from . import _device as D
 from . import _native as N
-from .hoqp import check_device_tensor
 from .rbd import STATE_BYTES, TARGET_BYTES
 from .sim import OUT_BYTES as SIM_OUT_BYTES
 
@@ -104,8 +104,7 @@ def lowlevel(c: N.LmpcLowlevelCfg, state: N.LmpcRbdState, target: N.LmpcWbcTarge
 
 def out_view(buf) -> np.ndarray:
     """uint8 [..., 400] (torch or NumPy) -> NumPy structured array [...] with the fields of lmpc_lowlevel_out."""
-    a = buf.cpu().numpy() if hasattr(buf, "cpu") else np.asarray(buf)
-    return np.ascontiguousarray(a, dtype=np.uint8).view(OUT_DTYPE)[..., 0]
+    return D.host_view(buf, OUT_DTYPE)
 
 
 def tau_view(d_out):
@@ -129,27 +128,15 @@ def lowlevel_device(c: N.LmpcLowlevelCfg, d_state, d_target, d_out, d_gait=None,
     [B][472] with d_candidates int32 [B][4] (both or neither): the plant's candidate contacts from the same launch."""
     import torch
 
-    B = int(d_state.shape[0]) if getattr(d_state, "dim", lambda: 0)() >= 1 else -1
-    dev = d_state.device if hasattr(d_state, "device") else None
-    check_device_tensor("d_state", d_state, torch.uint8, (B, STATE_BYTES), dev)
-    check_device_tensor("d_target", d_target, torch.uint8, (B, TARGET_BYTES), dev)
-    check_device_tensor("d_out", d_out, torch.uint8, (B, OUT_BYTES), dev)
-    gs = 0
-    if d_gait is not None:
-        if not getattr(d_gait, "is_cuda", False) or d_gait.device != dev or d_gait.dtype != torch.int32 or \
-                tuple(d_gait.shape) != (B,) or (B > 1 and d_gait.stride(0) < 1):
-            raise ValueError("d_gait: expected an int32 device tensor [B] on the states' device")
-        gs = int(d_gait.stride(0)) if B > 1 else 1
+    B, dev = D.batch("d_state", d_state)
+    D.check("d_state", d_state, torch.uint8, (B, STATE_BYTES), dev)
+    D.check("d_target", d_target, torch.uint8, (B, TARGET_BYTES), dev)
+    D.check("d_out", d_out, torch.uint8, (B, OUT_BYTES), dev)
+    gs = D.view("d_gait", d_gait, torch.int32, B, None, dev, optional=True)
     if (d_sim_out is None) != (d_candidates is None):
         raise ValueError("d_sim_out and d_candidates: both or neither")
-    if d_sim_out is not None:
-        check_device_tensor("d_sim_out", d_sim_out, torch.uint8, (B, SIM_OUT_BYTES), dev)
-        check_device_tensor("d_candidates", d_candidates, torch.int32, (B, 4), dev)
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
-
-    def ptr(t):
-        return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-    N.check(N.lib().lmpc_lowlevel_device(ctypes.byref(c), ptr(d_state), ptr(d_target), ptr(d_gait), gs, ptr(d_sim_out),
-                                         ptr(d_candidates), B, ptr(d_out), ctypes.c_void_p(s.cuda_stream)),
-            "lmpc_lowlevel_device")
+    D.check("d_sim_out", d_sim_out, torch.uint8, (B, SIM_OUT_BYTES), dev, optional=True)
+    D.check("d_candidates", d_candidates, torch.int32, (B, 4), dev, optional=True)
+    N.check(N.lib().lmpc_lowlevel_device(ctypes.byref(c), d_state.data_ptr(), d_target.data_ptr(), D.ptr(d_gait), gs,
+                                         D.ptr(d_sim_out), D.ptr(d_candidates), B, d_out.data_ptr(),
+                                         D.stream(stream, dev)), "lmpc_lowlevel_device")

@@ -18,8 +18,8 @@ import ctypes
 
 import numpy as np
 
+from . import _device as D
 from . import _native as N
-from .hoqp import check_device_tensor
 from .lowlevel import OUT_BYTES as LL_OUT_BYTES
 from .rbd import STATE_BYTES, TARGET_BYTES
 from .sim import OUT_BYTES as SIM_OUT_BYTES
@@ -64,20 +64,14 @@ def run_device(model: N.LmpcRbdModel, sim_cfg: N.LmpcSimCfg, ll_cfg: N.LmpcLowle
     `candidates` int32 [ticks][B][4]: row i is what tick i left."""
     import torch
 
-    B = int(d_state.shape[0]) if getattr(d_state, "dim", lambda: 0)() >= 1 else -1
-    dev = d_state.device if hasattr(d_state, "device") else None
+    B, dev = D.batch("d_state", d_state)
     ticks = int(ticks)
-    check_device_tensor("d_state", d_state, torch.uint8, (B, STATE_BYTES), dev)
-    check_device_tensor("d_target", d_target, torch.uint8, (B, TARGET_BYTES), dev)
-    check_device_tensor("d_sim_out", d_sim_out, torch.uint8, (B, SIM_OUT_BYTES), dev)
-    check_device_tensor("d_candidates", d_candidates, torch.int32, (B, 4), dev)
-    check_device_tensor("d_ll_out", d_ll_out, torch.uint8, (B, LL_OUT_BYTES), dev)
-    gs = 0
-    if d_gait is not None:
-        if not getattr(d_gait, "is_cuda", False) or d_gait.device != dev or d_gait.dtype != torch.int32 or \
-                tuple(d_gait.shape) != (B,) or (B > 1 and d_gait.stride(0) < 1):
-            raise ValueError("d_gait: expected an int32 device tensor [B] on the states' device")
-        gs = int(d_gait.stride(0)) if B > 1 else 1
+    D.check("d_state", d_state, torch.uint8, (B, STATE_BYTES), dev)
+    D.check("d_target", d_target, torch.uint8, (B, TARGET_BYTES), dev)
+    D.check("d_sim_out", d_sim_out, torch.uint8, (B, SIM_OUT_BYTES), dev)
+    D.check("d_candidates", d_candidates, torch.int32, (B, 4), dev)
+    D.check("d_ll_out", d_ll_out, torch.uint8, (B, LL_OUT_BYTES), dev)
+    gs = D.view("d_gait", d_gait, torch.int32, B, None, dev, optional=True)
     lg = None
     if logs:
         unknown = set(logs) - set(LOG_KEYS)
@@ -86,14 +80,9 @@ def run_device(model: N.LmpcRbdModel, sim_cfg: N.LmpcSimCfg, ll_cfg: N.LmpcLowle
         lg = N.LmpcLowsimLog()
         for key, t in logs.items():
             field, dtype, tail = LOG_KEYS[key]
-            check_device_tensor(f"logs[{key!r}]", t, getattr(torch, dtype), (max(ticks, 0), B) + tail, dev)
+            D.check(f"logs[{key!r}]", t, getattr(torch, dtype), (max(ticks, 0), B) + tail, dev)
             setattr(lg, field, t.data_ptr())
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
-
-    def ptr(t):
-        return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-    N.check(N.lib().lmpc_lowsim_run_device(ctypes.byref(model), ctypes.byref(sim_cfg), ctypes.byref(ll_cfg), ptr(d_state),
-                                           ptr(d_target), ptr(d_gait), gs, ptr(d_sim_out), ptr(d_candidates), ptr(d_ll_out),
-                                           B, ticks, int(substeps), None if lg is None else ctypes.byref(lg),
-                                           ctypes.c_void_p(s.cuda_stream)), "lmpc_lowsim_run_device")
+    N.check(N.lib().lmpc_lowsim_run_device(
+        ctypes.byref(model), ctypes.byref(sim_cfg), ctypes.byref(ll_cfg), d_state.data_ptr(), d_target.data_ptr(),
+        D.ptr(d_gait), gs, d_sim_out.data_ptr(), d_candidates.data_ptr(), d_ll_out.data_ptr(), B, ticks, int(substeps),
+        None if lg is None else ctypes.byref(lg), D.stream(stream, dev)), "lmpc_lowsim_run_device")

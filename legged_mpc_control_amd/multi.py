@@ -11,6 +11,7 @@ from typing import Sequence
 
 import numpy as np
 
+from . import _device as D
 from . import _native as N
 
 
@@ -29,6 +30,7 @@ class MultiDeviceSolver:
         self._M = N.multi_lib()
         self.H = int(horizon)
         self.devices = [int(d) for d in devices]
+        self.device = self.devices[0]  # the root: device-pointer batches live there
         arr = (ctypes.c_int32 * len(self.devices))(*self.devices)
         self._m = ctypes.c_void_p()
         N.check(self._M.lmpc_multi_create(ctypes.byref(params), self.H, arr, len(self.devices), ctypes.byref(self._m)),
@@ -45,40 +47,26 @@ class MultiDeviceSolver:
     def num_devices(self) -> int:
         return self._M.lmpc_multi_num_devices(self._m)
 
-    def _root_check(self, name, t, dtype, shape):
-        import torch
-
-        from .hoqp import check_device_tensor
-
-        check_device_tensor(name, t, dtype, shape, torch.device("cuda", self.devices[0]))
-
     def solve_commands_device(self, d_cmd, d_grf, d_status=None, d_iters=None, d_normals=None, stream=None):
         """Commands uint8 [B, 408] on devices[0] -> GRFs [B, H, 12] (+ status, iters) on devices[0]; synchronous."""
         import torch
 
-        B = int(d_cmd.shape[0])
-        self._root_check("d_cmd", d_cmd, torch.uint8, (B, N.COMMAND_BYTES))
-        self._root_check("d_grf", d_grf, torch.float64, (B, self.H, 12))
-        if d_status is not None:
-            self._root_check("d_status", d_status, torch.int32, (B,))
-        if d_iters is not None:
-            self._root_check("d_iters", d_iters, torch.int32, (B,))
-        if d_normals is not None:
-            self._root_check("d_normals", d_normals, torch.float64, (B, 4, 3))
-        if stream is None:
-            stream = torch.cuda.current_stream(self.devices[0])
-        sptr = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-        p = lambda t: None if t is None else t.data_ptr()
-        N.check(self._M.lmpc_multi_solve_commands_device(self._m, d_cmd.data_ptr(), p(d_normals), B, d_grf.data_ptr(),
-                                                         p(d_status), p(d_iters), sptr),
-                "lmpc_multi_solve_commands_device")
+        B, dev = D.batch("d_cmd", d_cmd, device=self.device)
+        D.check("d_cmd", d_cmd, torch.uint8, (B, N.COMMAND_BYTES), dev)
+        D.check("d_grf", d_grf, torch.float64, (B, self.H, 12), dev)
+        D.check("d_status", d_status, torch.int32, (B,), dev, optional=True)
+        D.check("d_iters", d_iters, torch.int32, (B,), dev, optional=True)
+        D.check("d_normals", d_normals, torch.float64, (B, 4, 3), dev, optional=True)
+        N.check(self._M.lmpc_multi_solve_commands_device(self._m, d_cmd.data_ptr(), D.ptr(d_normals), B,
+                                                         d_grf.data_ptr(), D.ptr(d_status), D.ptr(d_iters),
+                                                         D.stream(stream, dev)), "lmpc_multi_solve_commands_device")
 
     def solve_synth_device(self, cfg: N.LmpcSynthCfg, batch: int, seed: int, first_index: int = 0,
                            theta_max: float = -1.0):
         """Every device generates and solves its own shard; results gathered to devices[0] (torch tensors)."""
         import torch
 
-        dev = torch.device("cuda", self.devices[0])
+        dev = torch.device("cuda", self.device)
         grf = torch.empty((batch, self.H, 12), dtype=torch.float64, device=dev)
         st = torch.empty(batch, dtype=torch.int32, device=dev)
         it = torch.empty(batch, dtype=torch.int32, device=dev)

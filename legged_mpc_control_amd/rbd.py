@@ -22,8 +22,9 @@ import json
 
 import numpy as np
 
+from . import _device as D
 from . import _native as N
-from .hoqp import HoqpBatch, check_device_tensor
+from .hoqp import HoqpBatch
 from .wbc import WBC_RECORD_LEN
 
 MODEL_BYTES = ctypes.sizeof(N.LmpcRbdModel)    # 1432
@@ -140,28 +141,17 @@ def wbc_input_from_state(model: N.LmpcRbdModel, st: N.LmpcRbdState, tg: N.LmpcWb
     return s
 
 
-def _batch_device(d_state):
-    import torch
-
-    B = int(d_state.shape[0]) if d_state.dim() >= 1 else -1
-    dev = d_state.device if getattr(d_state, "is_cuda", False) else torch.device("cuda", torch.cuda.current_device())
-    return B, dev
-
-
 def wbc_inputs_device(model, d_state, d_target, d_inputs, stream=None):
     """A batch of WBC input blocks on the device (lmpc_wbc_inputs_device): d_state uint8 [B][288], d_target uint8
     [B][352], d_inputs uint8 [B][4848], all in HBM; asynchronous on `stream` (default: torch's current)."""
     import torch
 
-    B, dev = _batch_device(d_state)
-    check_device_tensor("d_state", d_state, torch.uint8, (B, STATE_BYTES), dev)
-    check_device_tensor("d_target", d_target, torch.uint8, (B, TARGET_BYTES), dev)
-    check_device_tensor("d_inputs", d_inputs, torch.uint8, (B, INPUT_BYTES), dev)
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
-    N.check(N.lib().lmpc_wbc_inputs_device(ctypes.byref(model), ctypes.c_void_p(d_state.data_ptr()),
-                                           ctypes.c_void_p(d_target.data_ptr()), B,
-                                           ctypes.c_void_p(d_inputs.data_ptr()), ctypes.c_void_p(s.cuda_stream)),
-            "lmpc_wbc_inputs_device")
+    B, dev = D.batch("d_state", d_state)
+    D.check("d_state", d_state, torch.uint8, (B, STATE_BYTES), dev)
+    D.check("d_target", d_target, torch.uint8, (B, TARGET_BYTES), dev)
+    D.check("d_inputs", d_inputs, torch.uint8, (B, INPUT_BYTES), dev)
+    N.check(N.lib().lmpc_wbc_inputs_device(ctypes.byref(model), d_state.data_ptr(), d_target.data_ptr(), B,
+                                           d_inputs.data_ptr(), D.stream(stream, dev)), "lmpc_wbc_inputs_device")
 
 
 def compute_device(model, d_state, d_terms, stream=None):
@@ -169,13 +159,11 @@ def compute_device(model, d_state, d_terms, stream=None):
     [B][5072]."""
     import torch
 
-    B, dev = _batch_device(d_state)
-    check_device_tensor("d_state", d_state, torch.uint8, (B, STATE_BYTES), dev)
-    check_device_tensor("d_terms", d_terms, torch.uint8, (B, TERMS_BYTES), dev)
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
-    N.check(N.lib().lmpc_rbd_compute_device(ctypes.byref(model), ctypes.c_void_p(d_state.data_ptr()), B,
-                                            ctypes.c_void_p(d_terms.data_ptr()), ctypes.c_void_p(s.cuda_stream)),
-            "lmpc_rbd_compute_device")
+    B, dev = D.batch("d_state", d_state)
+    D.check("d_state", d_state, torch.uint8, (B, STATE_BYTES), dev)
+    D.check("d_terms", d_terms, torch.uint8, (B, TERMS_BYTES), dev)
+    N.check(N.lib().lmpc_rbd_compute_device(ctypes.byref(model), d_state.data_ptr(), B, d_terms.data_ptr(),
+                                            D.stream(stream, dev)), "lmpc_rbd_compute_device")
 
 
 class WbcPipeline:
@@ -225,10 +213,8 @@ class WbcPipeline:
         import torch
         from .wbc import records_device
 
-        B = int(d_state.shape[0]) if d_state.dim() >= 1 else -1
-        if not 1 <= B <= self.max_batch:
-            raise ValueError(f"batch {B} outside 1..{self.max_batch}")
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        B, dev = D.batch("d_state", d_state, self.max_batch, self.device)
+        s = D.torch_stream(stream, dev)
         wbc_inputs_device(self.model, d_state, d_target, self.d_inputs[:B], s)
         records_device(self.d_inputs[:B], self.d_records[:B], s)
         d_act = None

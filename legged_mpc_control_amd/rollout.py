@@ -14,6 +14,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from . import _device as D
 from . import _native as N
 
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -93,16 +94,12 @@ def to_device(structs, device=None):
 
 def robots_from(buf):
     """uint8 [B, ROBOT_BYTES] (torch or NumPy) -> ctypes array of LmpcRobot (a copy on the host)."""
-    a = buf.cpu().numpy() if hasattr(buf, "cpu") else np.asarray(buf)
-    a = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1, N.ROBOT_BYTES)
-    return (N.LmpcRobot * a.shape[0]).from_buffer_copy(a.tobytes())
+    return D.host_structs(buf, N.LmpcRobot)
 
 
 def commands_from(buf):
     """uint8 [..., COMMAND_BYTES] (torch or NumPy) -> flat ctypes array of LmpcCommand (a copy on the host)."""
-    a = buf.cpu().numpy() if hasattr(buf, "cpu") else np.asarray(buf)
-    a = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1, N.COMMAND_BYTES)
-    return (N.LmpcCommand * a.shape[0]).from_buffer_copy(a.tobytes())
+    return D.host_structs(buf, N.LmpcCommand)
 
 
 ROBOT_DTYPE = np.dtype({
@@ -120,14 +117,12 @@ COMMAND_DTYPE = np.dtype({"names": ROBOT_DTYPE.names[:14], "formats": [ROBOT_DTY
 
 def robots_view(buf) -> np.ndarray:
     """uint8 [..., ROBOT_BYTES] -> NumPy structured array [...] with the fields of lmpc_robot (ROBOT_DTYPE)."""
-    a = buf.cpu().numpy() if hasattr(buf, "cpu") else np.asarray(buf)
-    return np.ascontiguousarray(a, dtype=np.uint8).view(ROBOT_DTYPE)[..., 0]
+    return D.host_view(buf, ROBOT_DTYPE)
 
 
 def commands_view(buf) -> np.ndarray:
     """uint8 [..., COMMAND_BYTES] -> NumPy structured array [...] with the fields of lmpc_command."""
-    a = buf.cpu().numpy() if hasattr(buf, "cpu") else np.asarray(buf)
-    return np.ascontiguousarray(a, dtype=np.uint8).view(COMMAND_DTYPE)[..., 0]
+    return D.host_view(buf, COMMAND_DTYPE)
 
 
 @dataclass

@@ -21,9 +21,9 @@ import ctypes
 
 import numpy as np
 
+from . import _device as D
 from . import _native as N
-from .hoqp import check_device_tensor
-from .rbd import STATE_BYTES, TARGET_BYTES, WbcPipeline, _batch_device
+from .rbd import STATE_BYTES, TARGET_BYTES, WbcPipeline
 
 CFG_BYTES = ctypes.sizeof(N.LmpcSimCfg)  # 24
 OUT_BYTES = ctypes.sizeof(N.LmpcSimOut)  # 472
@@ -83,46 +83,25 @@ def step(model, c: N.LmpcSimCfg, st, tau, contact, substeps: int = 1):
     return cur, o
 
 
-def _check_rows(name, t, dtype, B, width, dev):
-    """[B][width] of `dtype` on `dev`, unit stride within a row, any row stride >= width: a view is fine."""
-    if t is None or not getattr(t, "is_cuda", False):
-        raise ValueError(f"{name}: expected a device tensor")
-    if t.device != dev:
-        raise ValueError(f"{name}: on {t.device}, expected {dev}")
-    if t.dtype != dtype:
-        raise ValueError(f"{name}: dtype {t.dtype}, expected {dtype}")
-    if tuple(t.shape) != (B, width):
-        raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {(B, width)}")
-    if t.stride(1) != 1 or (B > 1 and t.stride(0) < width):
-        raise ValueError(f"{name}: strides {t.stride()}, expected (>= {width}, 1)")
-    return int(t.stride(0)) if B > 1 else width
-
-
-def _common(model, d_state, d_tau, d_contact, d_out):
+def _common(d_state, d_tau, d_contact, d_out, out_optional):
+    """The checks the two plant functions share -> (B, device, tau's row stride, the contacts' row stride)."""
     import torch
 
-    B, dev = _batch_device(d_state)
-    check_device_tensor("d_state", d_state, torch.uint8, (B, STATE_BYTES), dev)
-    ts = _check_rows("d_tau", d_tau, torch.float64, B, 12, dev)
-    cs = _check_rows("d_contact", d_contact, torch.int32, B, 4, dev)
-    if d_out is not None:
-        check_device_tensor("d_out", d_out, torch.uint8, (B, OUT_BYTES), dev)
+    B, dev = D.batch("d_state", d_state)
+    D.check("d_state", d_state, torch.uint8, (B, STATE_BYTES), dev)
+    ts = D.view("d_tau", d_tau, torch.float64, B, 12, dev)
+    cs = D.view("d_contact", d_contact, torch.int32, B, 4, dev)
+    D.check("d_out", d_out, torch.uint8, (B, OUT_BYTES), dev, optional=out_optional)
     return B, dev, ts, cs
 
 
 def forward_dynamics_device(model, d_state, d_tau, d_contact, d_out, unilateral=True, stream=None):
     """A batch of forward dynamics on the device (lmpc_rbd_forward_dynamics_device): d_state uint8 [B][288], d_tau
     float64 [B][12] and d_contact int32 [B][4] (views with any row stride), d_out uint8 [B][472]."""
-    import torch
-
-    if d_out is None:
-        raise ValueError("d_out: expected a device tensor")
-    B, dev, ts, cs = _common(model, d_state, d_tau, d_contact, d_out)
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    B, dev, ts, cs = _common(d_state, d_tau, d_contact, d_out, False)
     N.check(N.lib().lmpc_rbd_forward_dynamics_device(
-        ctypes.byref(model), ctypes.c_void_p(d_state.data_ptr()), ctypes.c_void_p(d_tau.data_ptr()), ts,
-        ctypes.c_void_p(d_contact.data_ptr()), cs, B, int(bool(unilateral)), ctypes.c_void_p(d_out.data_ptr()),
-        ctypes.c_void_p(s.cuda_stream)), "lmpc_rbd_forward_dynamics_device")
+        ctypes.byref(model), d_state.data_ptr(), d_tau.data_ptr(), ts, d_contact.data_ptr(), cs, B,
+        int(bool(unilateral)), d_out.data_ptr(), D.stream(stream, dev)), "lmpc_rbd_forward_dynamics_device")
 
 
 def step_device(model, c: N.LmpcSimCfg, d_state, d_tau, d_contact, d_next, d_out=None, substeps: int = 1, stream=None):
@@ -130,14 +109,11 @@ def step_device(model, c: N.LmpcSimCfg, d_state, d_tau, d_contact, d_next, d_out
     [B][288] (may be d_state itself); d_out may be None."""
     import torch
 
-    B, dev, ts, cs = _common(model, d_state, d_tau, d_contact, d_out)
-    check_device_tensor("d_next", d_next, torch.uint8, (B, STATE_BYTES), dev)
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    B, dev, ts, cs = _common(d_state, d_tau, d_contact, d_out, True)
+    D.check("d_next", d_next, torch.uint8, (B, STATE_BYTES), dev)
     N.check(N.lib().lmpc_sim_step_device(
-        ctypes.byref(model), ctypes.byref(c), ctypes.c_void_p(d_state.data_ptr()), ctypes.c_void_p(d_tau.data_ptr()), ts,
-        ctypes.c_void_p(d_contact.data_ptr()), cs, B, int(substeps), ctypes.c_void_p(d_next.data_ptr()),
-        ctypes.c_void_p(d_out.data_ptr() if d_out is not None else None), None, 0, ctypes.c_void_p(s.cuda_stream)),
-        "lmpc_sim_step_device")
+        ctypes.byref(model), ctypes.byref(c), d_state.data_ptr(), d_tau.data_ptr(), ts, d_contact.data_ptr(), cs, B,
+        int(substeps), d_next.data_ptr(), D.ptr(d_out), None, 0, D.stream(stream, dev)), "lmpc_sim_step_device")
 
 
 def target_contacts(d_target):
@@ -145,6 +121,14 @@ def target_contacts(d_target):
     import torch
 
     return d_target.view(torch.int32)[:, CONTACT_OFFSET:CONTACT_OFFSET + 4]
+
+
+def flags_view(d_out):
+    """The int32 [...][10] view of the tail of lmpc_sim_out inside packed outputs (uint8 [...][472]): held (4), touch
+    (4), status, reserved."""
+    import torch
+
+    return d_out.view(torch.int32)[..., N.LmpcSimOut.held.offset // 4:]
 
 
 class WbcSim:
@@ -177,27 +161,24 @@ class WbcSim:
         [ticks][B][42] (the tick's WBC solution) and wbc_iters int32 [ticks][B][3] (its iteration words)."""
         import torch
 
-        B = int(d_state.shape[0]) if d_state.dim() >= 1 else -1
-        if not 1 <= B <= self.max_batch:
-            raise ValueError(f"batch {B} outside 1..{self.max_batch}")
+        B, dev = D.batch("d_state", d_state, self.max_batch, self.device)
         if ticks < 0:
             raise ValueError("ticks must not be negative")
-        dev = torch.device("cuda", self.device)
-        check_device_tensor("d_target", d_target, torch.uint8, (B, TARGET_BYTES), dev)
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        D.check("d_state", d_state, torch.uint8, (B, STATE_BYTES), dev)
+        D.check("d_target", d_target, torch.uint8, (B, TARGET_BYTES), dev)
+        s = D.torch_stream(stream, dev)
         d_contact = target_contacts(d_target)
         d_out = self.d_out[:B]
         logs = None
         if log:
-            logs = dict(states=torch.empty((ticks, B, STATE_BYTES), dtype=torch.uint8, device=dev),
-                        held=torch.empty((ticks, B, 4), dtype=torch.int32, device=dev),
-                        touch=torch.empty((ticks, B, 4), dtype=torch.int32, device=dev),
-                        wbc_status=torch.empty((ticks, B), dtype=torch.int32, device=dev),
-                        sim_status=torch.empty((ticks, B), dtype=torch.int32, device=dev),
-                        x=torch.empty((ticks, B, self.pipeline.d_levels.shape[2]), dtype=torch.float64, device=dev),
-                        wbc_iters=torch.empty((ticks, B, self.pipeline.d_iters.shape[1]), dtype=torch.int32,
-                                              device=dev))
-            flags = d_out.view(torch.int32)[:, OUT_BYTES // 4 - 10:]  # held (4), touch (4), status, reserved
+            def buf(dtype, *tail):
+                return torch.empty((ticks, B) + tail, dtype=dtype, device=dev)
+
+            logs = dict(states=buf(torch.uint8, STATE_BYTES), held=buf(torch.int32, 4), touch=buf(torch.int32, 4),
+                        wbc_status=buf(torch.int32), sim_status=buf(torch.int32),
+                        x=buf(torch.float64, self.pipeline.d_levels.shape[2]),
+                        wbc_iters=buf(torch.int32, self.pipeline.d_iters.shape[1]))
+            flags = flags_view(d_out)
         with torch.cuda.stream(s):
             for t in range(ticks):
                 d_x, d_status = self.pipeline.solve_device(d_state, d_target, s)

@@ -18,6 +18,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
+from . import _device as D
 from . import _native as N
 
 
@@ -76,6 +77,7 @@ class BatchedConvexQPSolver:
         self._L = N.lib()
         self.H = int(horizon)
         self.max_batch = int(max_batch)
+        self.device = int(device)
         self.params = params
         self._ctx = ctypes.c_void_p()
         N.check(self._L.lmpc_create(ctypes.byref(params), self.H, self.max_batch, int(device),
@@ -193,116 +195,103 @@ class BatchedConvexQPSolver:
         normals: optional f64 device tensor [B,4,3] (terrain extension)."""
         import torch
 
-        B = rec.shape[0]
-        for t, dt in ((rec, torch.float64), (contact, torch.uint8), (grf, torch.float64)):
-            if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
-                raise ValueError("solve_device expects contiguous device tensors (f64 rec/grf, u8 contact)")
-        if rec.shape != (B, self.record_len) or contact.shape != (B, self.H, 4) or grf.shape != (B, self.H, 12):
-            raise ValueError("bad record/contact/grf shape")
-        if normals is not None and (not normals.is_cuda or normals.dtype != torch.float64 or
-                                    not normals.is_contiguous() or tuple(normals.shape) != (B, 4, 3)):
-            raise ValueError("normals must be a contiguous f64 device tensor [B, 4, 3]")
-        if stream is None:
-            stream = torch.cuda.current_stream(rec.device)
-        sptr = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        B, dev = D.batch("rec", rec, device=self.device)
+        D.check("rec", rec, torch.float64, (B, self.record_len), dev)
+        D.check("contact", contact, torch.uint8, (B, self.H, 4), dev)
+        self._check_results(B, dev, grf, status, iters, normals)
         N.check(self._L.lmpc_solve_batch_device_ex(
-            self._ctx, rec.data_ptr(), contact.data_ptr(), None if normals is None else normals.data_ptr(), B,
-            grf.data_ptr(), None if status is None else status.data_ptr(),
-            None if iters is None else iters.data_ptr(), sptr), "lmpc_solve_batch_device_ex")
+            self._ctx, rec.data_ptr(), contact.data_ptr(), D.ptr(normals), B, grf.data_ptr(), D.ptr(status),
+            D.ptr(iters), D.stream(stream, dev)), "lmpc_solve_batch_device_ex")
+
+    def _check_results(self, B, dev, grf, status, iters, normals, act_in=None, act_out=None):
+        """What every device solve writes (grf f64 [B, H, 12]; status, iters int32 [B] or None) and its optional
+        inputs (normals f64 [B, 4, 3]; active sets uint8 [B, H, 4])."""
+        import torch
+
+        D.check("grf", grf, torch.float64, (B, self.H, 12), dev)
+        D.check("status", status, torch.int32, (B,), dev, optional=True)
+        D.check("iters", iters, torch.int32, (B,), dev, optional=True)
+        D.check("normals", normals, torch.float64, (B, 4, 3), dev, optional=True)
+        D.check("act_in", act_in, torch.uint8, (B, self.H, 4), dev, optional=True)
+        D.check("act_out", act_out, torch.uint8, (B, self.H, 4), dev, optional=True)
 
     # ---- the step before the QP, on the device (SURVEY.md 8f-1) -------------------------------
     # Commands live in HBM as an opaque uint8 tensor [B, N.COMMAND_BYTES] (lmpc_command array).
-    @staticmethod
-    def _stream(stream, dev):
+    def _commands(self, cmd):
+        """(B, device) of a call on commands uint8 [B, 408], checked."""
         import torch
 
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        return stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        B, dev = D.batch("cmd", cmd, device=self.device)
+        D.check("cmd", cmd, torch.uint8, (B, N.COMMAND_BYTES), dev)
+        return B, dev
+
+    def _out_device(self, device):
+        import torch
+
+        return torch.device("cuda", self.device) if device is None else device
 
     def synth_commands_device(self, cfg: N.LmpcSynthCfg, count: int, seed: int, first_index: int = 0, device=None,
                               stream=None):
-        """Synthetic commands generated on the device from (seed, global index) -> uint8 [count, 408]."""
+        """Synthetic commands generated on the device from (seed, global index) -> uint8 [count, 408] (on the
+        context's device unless `device` is given)."""
         import torch
 
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        dev = self._out_device(device)
         out = torch.empty((count, N.COMMAND_BYTES), dtype=torch.uint8, device=dev)
         N.check(self._L.lmpc_synth_commands_device(self._ctx, ctypes.byref(cfg), seed, first_index, count,
-                                                   out.data_ptr(), self._stream(stream, dev)),
-                "lmpc_synth_commands_device")
+                                                   out.data_ptr(), D.stream(stream, dev)), "lmpc_synth_commands_device")
         return out
 
     def synth_normals_device(self, count: int, seed: int, first_index: int = 0, theta_max: float = 0.3, device=None,
                              stream=None):
         import torch
 
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        dev = self._out_device(device)
         out = torch.empty((count, 4, 3), dtype=torch.float64, device=dev)
         N.check(self._L.lmpc_synth_normals_device(self._ctx, seed, first_index, count, float(theta_max),
-                                                  out.data_ptr(), self._stream(stream, dev)),
-                "lmpc_synth_normals_device")
+                                                  out.data_ptr(), D.stream(stream, dev)), "lmpc_synth_normals_device")
         return out
 
     def build_records_device(self, cmd, stream=None):
         """uint8 [B, 408] commands in HBM -> (rec [B, 33+12H] f64, contact [B, H, 4] u8) in HBM."""
         import torch
 
-        B = cmd.shape[0]
-        if not cmd.is_cuda or cmd.dtype != torch.uint8 or tuple(cmd.shape) != (B, N.COMMAND_BYTES):
-            raise ValueError("commands must be a uint8 device tensor [B, COMMAND_BYTES]")
-        rec = torch.empty((B, self.record_len), dtype=torch.float64, device=cmd.device)
-        con = torch.empty((B, self.H, 4), dtype=torch.uint8, device=cmd.device)
+        B, dev = self._commands(cmd)
+        rec = torch.empty((B, self.record_len), dtype=torch.float64, device=dev)
+        con = torch.empty((B, self.H, 4), dtype=torch.uint8, device=dev)
         N.check(self._L.lmpc_build_records_device(self._ctx, cmd.data_ptr(), B, rec.data_ptr(), con.data_ptr(),
-                                                  self._stream(stream, cmd.device)), "lmpc_build_records_device")
+                                                  D.stream(stream, dev)), "lmpc_build_records_device")
         return rec, con
 
     def solve_commands_device(self, cmd, grf, status=None, iters=None, stream=None, normals=None) -> None:
         """commands -> records (context buffers) -> solve, all on `stream`."""
-        import torch
-
-        B = cmd.shape[0]
-        if not cmd.is_cuda or cmd.dtype != torch.uint8 or tuple(cmd.shape) != (B, N.COMMAND_BYTES):
-            raise ValueError("commands must be a uint8 device tensor [B, COMMAND_BYTES]")
-        if grf.shape != (B, self.H, 12) or grf.dtype != torch.float64 or not grf.is_cuda:
-            raise ValueError("bad grf tensor")
+        B, dev = self._commands(cmd)
+        self._check_results(B, dev, grf, status, iters, normals)
         N.check(self._L.lmpc_solve_commands_device(
-            self._ctx, cmd.data_ptr(), None if normals is None else normals.data_ptr(), B, grf.data_ptr(),
-            None if status is None else status.data_ptr(), None if iters is None else iters.data_ptr(),
-            self._stream(stream, cmd.device)), "lmpc_solve_commands_device")
+            self._ctx, cmd.data_ptr(), D.ptr(normals), B, grf.data_ptr(), D.ptr(status), D.ptr(iters),
+            D.stream(stream, dev)), "lmpc_solve_commands_device")
 
     # ---- warm start and the closed-loop rollout on the device (include/lmpc/lmpc_rollout.h) ------------
     def shift_active_set_device(self, act, stream=None):
         """uint8 [B, H, 4] active sets in HBM -> the sets one MPC step later (a new tensor; lmpc_shift_active_set_device)."""
         import torch
 
-        B = act.shape[0]
-        if not act.is_cuda or act.dtype != torch.uint8 or not act.is_contiguous() or tuple(act.shape) != (B, self.H, 4):
-            raise ValueError("act must be a contiguous uint8 device tensor [B, H, 4]")
+        B, dev = D.batch("act", act, device=self.device)
+        D.check("act", act, torch.uint8, (B, self.H, 4), dev)
         out = torch.empty_like(act)
         N.check(self._L.lmpc_shift_active_set_device(self._ctx, act.data_ptr(), B, out.data_ptr(),
-                                                     self._stream(stream, act.device)), "lmpc_shift_active_set_device")
+                                                     D.stream(stream, dev)), "lmpc_shift_active_set_device")
         return out
 
     def solve_commands_warm_device(self, cmd, grf, act_in=None, act_out=None, status=None, iters=None, stream=None,
                                    normals=None) -> None:
         """lmpc_solve_batch_warm on device buffers: commands -> records -> the scratch Riccati kernel from act_in
         (uint8 [B, H, 4] or None = cold), the verified sets into act_out (or None); asynchronous on `stream`."""
-        import torch
-
-        B = cmd.shape[0]
-        if not cmd.is_cuda or cmd.dtype != torch.uint8 or tuple(cmd.shape) != (B, N.COMMAND_BYTES) or \
-                not cmd.is_contiguous():
-            raise ValueError("commands must be a contiguous uint8 device tensor [B, COMMAND_BYTES]")
-        if grf.shape != (B, self.H, 12) or grf.dtype != torch.float64 or not grf.is_cuda or not grf.is_contiguous():
-            raise ValueError("bad grf tensor")
-        for a in (act_in, act_out):
-            if a is not None and (not a.is_cuda or a.dtype != torch.uint8 or not a.is_contiguous() or
-                                  tuple(a.shape) != (B, self.H, 4)):
-                raise ValueError("active sets must be contiguous uint8 device tensors [B, H, 4]")
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        B, dev = self._commands(cmd)
+        self._check_results(B, dev, grf, status, iters, normals, act_in, act_out)
         N.check(self._L.lmpc_solve_commands_warm_device(
-            self._ctx, cmd.data_ptr(), ptr(normals), B, ptr(act_in), ptr(act_out), grf.data_ptr(), ptr(status),
-            ptr(iters), self._stream(stream, cmd.device)), "lmpc_solve_commands_warm_device")
+            self._ctx, cmd.data_ptr(), D.ptr(normals), B, D.ptr(act_in), D.ptr(act_out), grf.data_ptr(), D.ptr(status),
+            D.ptr(iters), D.stream(stream, dev)), "lmpc_solve_commands_warm_device")
 
     def rollout_device(self, robots, ticks: int, act=None, log=False, stream=None, cfg=None):
         """`ticks` closed-loop MPC ticks for the robots (uint8 device tensor [B, ROBOT_BYTES], updated in place;
@@ -315,24 +304,26 @@ class BatchedConvexQPSolver:
 
         from . import rollout as R
 
-        B = robots.shape[0]
-        if not robots.is_cuda or robots.dtype != torch.uint8 or not robots.is_contiguous() or \
-                tuple(robots.shape) != (B, N.ROBOT_BYTES):
-            raise ValueError("robots must be a contiguous uint8 device tensor [B, ROBOT_BYTES]")
-        if act is not None and (not act.is_cuda or act.dtype != torch.uint8 or not act.is_contiguous() or
-                                tuple(act.shape) != (B, self.H, 4)):
-            raise ValueError("act must be a contiguous uint8 device tensor [B, H, 4]")
+        B, dev = D.batch("robots", robots, device=self.device)
+        D.check("robots", robots, torch.uint8, (B, N.ROBOT_BYTES), dev)
+        D.check("act", act, torch.uint8, (B, self.H, 4), dev, optional=True)
         if cfg is None:
             cfg = R.cfg_go1()
         if log is True:
-            log = R.alloc_log(int(ticks), B, robots.device)
-        lg = log.struct() if log else None
-        if log and (log.x.shape[0] < ticks or log.x.shape[1] != B):
-            raise ValueError("the log holds fewer ticks than asked for, or another batch")
-        N.check(self._L.lmpc_rollout_device(self._ctx, ctypes.byref(cfg), robots.data_ptr(),
-                                            None if act is None else act.data_ptr(), B, int(ticks),
-                                            None if lg is None else ctypes.byref(lg),
-                                            self._stream(stream, robots.device)), "lmpc_rollout_device")
+            log = R.alloc_log(int(ticks), B, dev)
+        lg = None
+        if log:
+            T, _ = D.batch("log.x", log.x)  # a log may hold more ticks than this call fills
+            if T < ticks:
+                raise ValueError(f"the log holds {T} ticks, fewer than the {ticks} asked for")
+            for name, dtype, tail in (("cmd", torch.uint8, (N.COMMAND_BYTES,)), ("u0", torch.float64, (12,)),
+                                      ("x", torch.float64, (12,)), ("status", torch.int32, ()),
+                                      ("iters", torch.int32, ())):
+                D.check(f"log.{name}", getattr(log, name), dtype, (T, B) + tail, dev)
+            lg = log.struct()
+        N.check(self._L.lmpc_rollout_device(self._ctx, ctypes.byref(cfg), robots.data_ptr(), D.ptr(act), B, int(ticks),
+                                            None if lg is None else ctypes.byref(lg), D.stream(stream, dev)),
+                "lmpc_rollout_device")
         return log or None
 
     # ---- the step after the QP: GRF -> joint torque ------------------------------
@@ -340,15 +331,13 @@ class BatchedConvexQPSolver:
         """tau [B, 12] = -J'(R'u0) per leg, from rec (R), joint_pos [B, 12] and grf [B, H, 12] in HBM."""
         import torch
 
-        B = rec.shape[0]
-        for t in (rec, joint_pos, grf):
-            if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
-                raise ValueError("grf_to_torque_device expects contiguous f64 device tensors")
-        if joint_pos.shape != (B, 12) or grf.shape != (B, self.H, 12) or rec.shape != (B, self.record_len):
-            raise ValueError("bad rec/joint_pos/grf shape")
-        tau = torch.empty((B, 12), dtype=torch.float64, device=rec.device)
+        B, dev = D.batch("rec", rec, device=self.device)
+        D.check("rec", rec, torch.float64, (B, self.record_len), dev)
+        D.check("joint_pos", joint_pos, torch.float64, (B, 12), dev)
+        D.check("grf", grf, torch.float64, (B, self.H, 12), dev)
+        tau = torch.empty((B, 12), dtype=torch.float64, device=dev)
         N.check(self._L.lmpc_grf_to_torque_device(self._ctx, ctypes.byref(kin), rec.data_ptr(), joint_pos.data_ptr(),
-                                                  grf.data_ptr(), B, tau.data_ptr(), self._stream(stream, rec.device)),
+                                                  grf.data_ptr(), B, tau.data_ptr(), D.stream(stream, dev)),
                 "lmpc_grf_to_torque_device")
         return tau
 

@@ -29,13 +29,13 @@ import ctypes
 
 import numpy as np
 
+from . import _device as D
 from . import _native as N
 from . import contact as C
 from . import est as E
 from . import lowlevel as LL
 from . import lowsim as LS
 from . import sim as S
-from .hoqp import check_device_tensor
 from .rbd import STATE_BYTES, TARGET_BYTES, WbcPipeline, target as wbc_target
 from .solver import BatchedConvexQPSolver
 
@@ -104,22 +104,12 @@ def to_bytes(structs) -> np.ndarray:
 
 def robots_from(buf):
     """uint8 [B, 960] (torch or NumPy) -> ctypes array of LmpcStackRobot (a copy on the host)."""
-    a = buf.cpu().numpy() if hasattr(buf, "cpu") else np.asarray(buf)
-    a = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1, ROBOT_BYTES)
-    return (N.LmpcStackRobot * a.shape[0]).from_buffer_copy(a.tobytes())
+    return D.host_structs(buf, N.LmpcStackRobot)
 
 
 def robots_view(buf) -> np.ndarray:
     """uint8 [..., 960] -> NumPy structured array [...] with the fields of lmpc_stack_robot (STACK_ROBOT_DTYPE)."""
-    a = buf.cpu().numpy() if hasattr(buf, "cpu") else np.asarray(buf)
-    return np.ascontiguousarray(a, dtype=np.uint8).view(STACK_ROBOT_DTYPE)[..., 0]
-
-
-def _stream(stream, dev):
-    import torch
-
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
-    return s, ctypes.c_void_p(s.cuda_stream)
+    return D.host_view(buf, STACK_ROBOT_DTYPE)
 
 
 def advance_device(solver: BatchedConvexQPSolver, cfg: N.LmpcRolloutCfg, d_robots, d_state, d_sim_out, stream=None):
@@ -128,14 +118,13 @@ def advance_device(solver: BatchedConvexQPSolver, cfg: N.LmpcRolloutCfg, d_robot
     `solve_device` then solves."""
     import torch
 
-    B = int(d_robots.shape[0]) if d_robots.dim() >= 1 else -1
-    dev = d_robots.device
-    check_device_tensor("d_robots", d_robots, torch.uint8, (B, ROBOT_BYTES), dev)
-    check_device_tensor("d_state", d_state, torch.uint8, (B, STATE_BYTES), dev)
-    check_device_tensor("d_sim_out", d_sim_out, torch.uint8, (B, S.OUT_BYTES), dev)
-    _, sp = _stream(stream, dev)
+    B, dev = D.batch("d_robots", d_robots, device=solver.device)
+    D.check("d_robots", d_robots, torch.uint8, (B, ROBOT_BYTES), dev)
+    D.check("d_state", d_state, torch.uint8, (B, STATE_BYTES), dev)
+    D.check("d_sim_out", d_sim_out, torch.uint8, (B, S.OUT_BYTES), dev)
     N.check(N.lib().lmpc_stack_advance_device(solver._ctx, ctypes.byref(cfg), d_robots.data_ptr(), d_state.data_ptr(),
-                                              d_sim_out.data_ptr(), B, sp), "lmpc_stack_advance_device")
+                                              d_sim_out.data_ptr(), B, D.stream(stream, dev)),
+            "lmpc_stack_advance_device")
 
 
 def solve_device(solver: BatchedConvexQPSolver, d_grf, d_status=None, d_iters=None, stream=None):
@@ -143,30 +132,25 @@ def solve_device(solver: BatchedConvexQPSolver, d_grf, d_status=None, d_iters=No
     [B][H][12], d_status / d_iters int32 [B] or None."""
     import torch
 
-    B = int(d_grf.shape[0]) if d_grf.dim() >= 1 else -1
-    dev = d_grf.device
-    check_device_tensor("d_grf", d_grf, torch.float64, (B, solver.H, 12), dev)
-    for name, t in (("d_status", d_status), ("d_iters", d_iters)):
-        if t is not None:
-            check_device_tensor(name, t, torch.int32, (B,), dev)
-    _, sp = _stream(stream, dev)
-    N.check(N.lib().lmpc_stack_solve_device(solver._ctx, B, d_grf.data_ptr(),
-                                            None if d_status is None else d_status.data_ptr(),
-                                            None if d_iters is None else d_iters.data_ptr(), sp),
-            "lmpc_stack_solve_device")
+    B, dev = D.batch("d_grf", d_grf, device=solver.device)
+    D.check("d_grf", d_grf, torch.float64, (B, solver.H, 12), dev)
+    D.check("d_status", d_status, torch.int32, (B,), dev, optional=True)
+    D.check("d_iters", d_iters, torch.int32, (B,), dev, optional=True)
+    N.check(N.lib().lmpc_stack_solve_device(solver._ctx, B, d_grf.data_ptr(), D.ptr(d_status), D.ptr(d_iters),
+                                            D.stream(stream, dev)), "lmpc_stack_solve_device")
 
 
 def context_records(solver: BatchedConvexQPSolver, batch: int, stream=None):
-    """Copies (device tensors) of the first `batch` records [batch][33 + 12 H] and contact schedules [batch][H][4] in
-    `solver`'s own buffers, as the last expansion left them (lmpc_stack_copy_records_device)."""
+    """Copies (device tensors, on the solver's device) of the first `batch` records [batch][33 + 12 H] and contact
+    schedules [batch][H][4] in `solver`'s own buffers, as the last expansion left them
+    (lmpc_stack_copy_records_device)."""
     import torch
 
-    dev = torch.device("cuda", torch.cuda.current_device())
+    dev = torch.device("cuda", solver.device)
     d_rec = torch.empty((batch, solver.record_len), dtype=torch.float64, device=dev)
     d_con = torch.empty((batch, solver.H, 4), dtype=torch.uint8, device=dev)
-    _, sp = _stream(stream, dev)
-    N.check(N.lib().lmpc_stack_copy_records_device(solver._ctx, int(batch), d_rec.data_ptr(), d_con.data_ptr(), sp),
-            "lmpc_stack_copy_records_device")
+    N.check(N.lib().lmpc_stack_copy_records_device(solver._ctx, int(batch), d_rec.data_ptr(), d_con.data_ptr(),
+                                                   D.stream(stream, dev)), "lmpc_stack_copy_records_device")
     return d_rec, d_con
 
 
@@ -175,17 +159,14 @@ def targets_device(d_robots, d_grf, template: N.LmpcWbcTarget, d_target, stream=
     [B][H][12] or [B][12] (u_0 is read by stride); d_target uint8 [B][352]."""
     import torch
 
-    B = int(d_robots.shape[0]) if d_robots.dim() >= 1 else -1
-    dev = d_robots.device
-    check_device_tensor("d_robots", d_robots, torch.uint8, (B, ROBOT_BYTES), dev)
-    check_device_tensor("d_target", d_target, torch.uint8, (B, TARGET_BYTES), dev)
-    if d_grf is None or not getattr(d_grf, "is_cuda", False) or d_grf.device != dev or d_grf.dtype != torch.float64 or \
-            d_grf.dim() not in (2, 3) or d_grf.shape[0] != B or d_grf.shape[-1] != 12 or not d_grf.is_contiguous():
-        raise ValueError("d_grf: expected a contiguous float64 device tensor [B][H][12] or [B][12]")
-    stride = d_grf.numel() // B
-    _, sp = _stream(stream, dev)
-    N.check(N.lib().lmpc_stack_targets_device(d_robots.data_ptr(), d_grf.data_ptr(), stride, ctypes.byref(template), B,
-                                              d_target.data_ptr(), sp), "lmpc_stack_targets_device")
+    B, dev = D.batch("d_robots", d_robots)
+    D.check("d_robots", d_robots, torch.uint8, (B, ROBOT_BYTES), dev)
+    D.check("d_target", d_target, torch.uint8, (B, TARGET_BYTES), dev)
+    horizon = tuple(getattr(d_grf, "shape", ()))[1:2]  # (H,) of a 3-d d_grf: any H
+    D.check("d_grf", d_grf, torch.float64, (B, 12), dev, allow_shape=(B,) + horizon + (12,))
+    N.check(N.lib().lmpc_stack_targets_device(d_robots.data_ptr(), d_grf.data_ptr(), d_grf.numel() // B,
+                                              ctypes.byref(template), B, d_target.data_ptr(), D.stream(stream, dev)),
+            "lmpc_stack_targets_device")
 
 
 def candidates_device(d_sim_out, d_candidates, stream=None):
@@ -193,13 +174,11 @@ def candidates_device(d_sim_out, d_candidates, stream=None):
     d_sim_out uint8 [B][472], d_candidates int32 [B][4]."""
     import torch
 
-    B = int(d_sim_out.shape[0]) if d_sim_out.dim() >= 1 else -1
-    dev = d_sim_out.device
-    check_device_tensor("d_sim_out", d_sim_out, torch.uint8, (B, S.OUT_BYTES), dev)
-    check_device_tensor("d_candidates", d_candidates, torch.int32, (B, 4), dev)
-    _, sp = _stream(stream, dev)
-    N.check(N.lib().lmpc_stack_candidates_device(d_sim_out.data_ptr(), B, d_candidates.data_ptr(), sp),
-            "lmpc_stack_candidates_device")
+    B, dev = D.batch("d_sim_out", d_sim_out)
+    D.check("d_sim_out", d_sim_out, torch.uint8, (B, S.OUT_BYTES), dev)
+    D.check("d_candidates", d_candidates, torch.int32, (B, 4), dev)
+    N.check(N.lib().lmpc_stack_candidates_device(d_sim_out.data_ptr(), B, d_candidates.data_ptr(),
+                                                 D.stream(stream, dev)), "lmpc_stack_candidates_device")
 
 
 class StackLoop:
@@ -334,16 +313,13 @@ class StackLoop:
         the noise of low-level tick n (counted from the filters' initialisation, from 1) is keyed (seed, robot, n)."""
         import torch
 
-        B = int(d_robots.shape[0]) if d_robots.dim() >= 1 else -1
-        if not 1 <= B <= self.max_batch:
-            raise ValueError(f"batch {B} outside 1..{self.max_batch}")
+        B, dev = D.batch("d_robots", d_robots, self.max_batch, self.device)
         if mpc_ticks < 0:
             raise ValueError("mpc_ticks must not be negative")
-        dev = torch.device("cuda", self.device)
-        check_device_tensor("d_robots", d_robots, torch.uint8, (B, ROBOT_BYTES), dev)
-        check_device_tensor("d_state", d_state, torch.uint8, (B, STATE_BYTES), dev)
-        check_device_tensor("d_sim_out", d_sim_out, torch.uint8, (B, S.OUT_BYTES), dev)
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        D.check("d_robots", d_robots, torch.uint8, (B, ROBOT_BYTES), dev)
+        D.check("d_state", d_state, torch.uint8, (B, STATE_BYTES), dev)
+        D.check("d_sim_out", d_sim_out, torch.uint8, (B, S.OUT_BYTES), dev)
+        s = D.torch_stream(stream, dev)
         T, W = int(mpc_ticks), self.wbc_per_mpc
         d_grf, d_qst, d_qit = self.d_grf[:B], self.d_qp_status[:B], self.d_qp_iters[:B]
         d_target, d_cand = self.d_target[:B], self.d_candidates[:B]
@@ -361,26 +337,26 @@ class StackLoop:
         logs = None
         if log:
             K = T * W
-            logs = dict(robots=torch.empty((T, B, ROBOT_BYTES), dtype=torch.uint8, device=dev),
-                        u0=torch.empty((T, B, 12), dtype=torch.float64, device=dev),
-                        qp_status=torch.empty((T, B), dtype=torch.int32, device=dev),
-                        qp_iters=torch.empty((T, B), dtype=torch.int32, device=dev),
-                        target=torch.empty((T, B, TARGET_BYTES), dtype=torch.uint8, device=dev),
-                        states=torch.empty((K, B, STATE_BYTES), dtype=torch.uint8, device=dev),
-                        out=torch.empty((K, B, S.OUT_BYTES), dtype=torch.uint8, device=dev),
-                        tau=torch.empty((K, B, 12), dtype=torch.float64, device=dev),
-                        candidates=torch.empty((K, B, 4), dtype=torch.int32, device=dev))
+
+            def buf(rows, dtype, *tail):
+                return torch.empty((rows, B) + tail, dtype=dtype, device=dev)
+
+            logs = dict(robots=buf(T, torch.uint8, ROBOT_BYTES), u0=buf(T, torch.float64, 12),
+                        qp_status=buf(T, torch.int32), qp_iters=buf(T, torch.int32),
+                        target=buf(T, torch.uint8, TARGET_BYTES), states=buf(K, torch.uint8, STATE_BYTES),
+                        out=buf(K, torch.uint8, S.OUT_BYTES), tau=buf(K, torch.float64, 12),
+                        candidates=buf(K, torch.int32, 4))
             if ll is None:
-                logs["wbc_status"] = torch.empty((K, B), dtype=torch.int32, device=dev)
-                logs["wbc_iters"] = torch.empty((K, B, self.pipeline.d_iters.shape[1]), dtype=torch.int32, device=dev)
+                logs["wbc_status"] = buf(K, torch.int32)
+                logs["wbc_iters"] = buf(K, torch.int32, self.pipeline.d_iters.shape[1])
             else:
-                logs["ll_out"] = torch.empty((K, B, LL.OUT_BYTES), dtype=torch.uint8, device=dev)
+                logs["ll_out"] = buf(K, torch.uint8, LL.OUT_BYTES)
             if plant is not None:
-                logs["contact_out"] = torch.empty((K, B, C.OUT_BYTES), dtype=torch.uint8, device=dev)
+                logs["contact_out"] = buf(K, torch.uint8, C.OUT_BYTES)
             if est is not None:
                 for name, width in (("sensors", E.SENSORS_BYTES), ("state_est", STATE_BYTES), ("filter", E.FILTER_BYTES),
                                     ("est_out", E.OUT_BYTES), ("shadow", S.OUT_BYTES)):
-                    logs[name] = torch.empty((K, B, width), dtype=torch.uint8, device=dev)
+                    logs[name] = buf(K, torch.uint8, width)
         with torch.cuda.stream(s):
             if est is not None:
                 if self._est_batch != B:
@@ -446,7 +422,7 @@ class StackLoop:
                             logs["est_out"][k].copy_(d_eout)
                             logs["shadow"][k].copy_(d_fb_out)
         if log:
-            flags = logs["out"].view(torch.int32)[..., S.OUT_BYTES // 4 - 10:]  # held (4), touch (4), status, reserved
+            flags = S.flags_view(logs["out"])
             logs["cmd"] = logs["robots"][..., :N.COMMAND_BYTES]
             logs["held"], logs["touch"], logs["sim_status"] = flags[..., 0:4], flags[..., 4:8], flags[..., 8]
             if ll is not None:

@@ -193,16 +193,13 @@ def records_device(d_inputs, d_records, stream=None):
 
     import torch
 
+    from . import _device as D
     from ._native import LmpcWbcInput, check, lib
-    from .hoqp import check_device_tensor
 
-    s = stream if stream is not None else torch.cuda.current_stream()
-    B = int(d_inputs.shape[0]) if d_inputs.dim() >= 1 else -1
-    dev = d_inputs.device if getattr(d_inputs, "is_cuda", False) else torch.device("cuda", torch.cuda.current_device())
-    check_device_tensor("d_inputs", d_inputs, torch.uint8, (B, ctypes.sizeof(LmpcWbcInput)), dev)
-    check_device_tensor("d_records", d_records, torch.float64, (B, WBC_RECORD_LEN), dev)
-    check(lib().lmpc_wbc_tasks_device(ctypes.c_void_p(d_inputs.data_ptr()), d_inputs.shape[0],
-                                      ctypes.c_void_p(d_records.data_ptr()), ctypes.c_void_p(s.cuda_stream)),
+    B, dev = D.batch("d_inputs", d_inputs)
+    D.check("d_inputs", d_inputs, torch.uint8, (B, ctypes.sizeof(LmpcWbcInput)), dev)
+    D.check("d_records", d_records, torch.float64, (B, WBC_RECORD_LEN), dev)
+    check(lib().lmpc_wbc_tasks_device(d_inputs.data_ptr(), B, d_records.data_ptr(), D.stream(stream, dev)),
           "lmpc_wbc_tasks_device")
 
 

@@ -26,7 +26,7 @@
 //   solves          U'y = r, U x = y tile by tile on the matrix cores (vectors replicated across
 //                   the 16 accumulator columns, so every product feeds the next without LDS).
 // The leg-level interior point and active-set polish are those of the Riccati path
-// (lmpc_kernels.hip), with one stance leg-step per lane.
+// (their steps: lmpc_qp_step.h), with one stance leg-step per lane.
 #include <hip/hip_runtime.h>
 
 #include <cmath>

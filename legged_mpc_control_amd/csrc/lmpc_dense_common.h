@@ -27,6 +27,7 @@
 #include "lmpc/lmpc.h"
 #include "lmpc_device.h"
 #include "lmpc_kernel_common.h"
+#include "lmpc_qp_step.h"
 
 namespace lmpc {
 
@@ -763,75 +764,23 @@ __device__ __forceinline__ int dense_prologue(const DevParams& prm, const DSmem&
         S.fb[lane] = __popcll(below);
     }
     if (TERRAIN && lane < 4) {
-        const double* nin = normals + (size_t)qp * 12 + 3 * lane;
-        const double n0 = nin[0], n1 = nin[1], n2 = nin[2];
-        const double nn = sqrt(n0 * n0 + n1 * n1 + n2 * n2);
-        const double nx = n0 / nn, ny = n1 / nn, c = n2 / nn;
-        const double h = 1.0 / (1.0 + c);
-        const double R[9] = {1.0 - nx * nx * h, -nx * ny * h, nx, -nx * ny * h, 1.0 - ny * ny * h, ny, -nx, -ny, c};
+        double R[9];
+        terrain_frame(normals + (size_t)qp * 12 + 3 * lane, R);
 #pragma unroll
         for (int e = 0; e < 9; ++e) S.tf[9 * lane + e] = R[e];
     }
     LMPC_SYNC();
     double iw[9];
-    {
-        const ldouble* R = S.hdr + LMPC_REC_ROT;
-        double RI[9], Iw[9];
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j)
-                RI[i * 3 + j] = R[i * 3 + 0] * prm.Ib[0 * 3 + j] + R[i * 3 + 1] * prm.Ib[1 * 3 + j] + R[i * 3 + 2] * prm.Ib[2 * 3 + j];
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j)
-                Iw[i * 3 + j] = RI[i * 3 + 0] * R[j * 3 + 0] + RI[i * 3 + 1] * R[j * 3 + 1] + RI[i * 3 + 2] * R[j * 3 + 2];
-        const double c00 = Iw[4] * Iw[8] - Iw[5] * Iw[7];
-        const double c01 = Iw[5] * Iw[6] - Iw[3] * Iw[8];
-        const double c02 = Iw[3] * Iw[7] - Iw[4] * Iw[6];
-        const double id = 1.0 / (Iw[0] * c00 + Iw[1] * c01 + Iw[2] * c02);
-        iw[0] = c00 * id;
-        iw[1] = (Iw[2] * Iw[7] - Iw[1] * Iw[8]) * id;
-        iw[2] = (Iw[1] * Iw[5] - Iw[2] * Iw[4]) * id;
-        iw[3] = c01 * id;
-        iw[4] = (Iw[0] * Iw[8] - Iw[2] * Iw[6]) * id;
-        iw[5] = (Iw[2] * Iw[3] - Iw[0] * Iw[5]) * id;
-        iw[6] = c02 * id;
-        iw[7] = (Iw[1] * Iw[6] - Iw[0] * Iw[7]) * id;
-        iw[8] = (Iw[0] * Iw[4] - Iw[1] * Iw[3]) * id;
-    }
-    for (int k = lane; k < H; k += 64) {
-        double sn, cn;
-        sincos(S.xr[12 * k + 2], &sn, &cn);
-        S.cs[2 * k] = cn;
-        S.cs[2 * k + 1] = sn;
-    }
+    world_inertia_inv(S.hdr + LMPC_REC_ROT, prm.Ib, iw);
+    yaw_cos_sin(S.xr, S.cs, H, lane);
     for (int e = lane; e < 72; e += 64) {
-        const int r = e / 12, c = e % 12, j = c / 3, cc = c % 3;
-        double w[3];
-        if (r < 3) {
-            const ldouble* ft = S.hdr + LMPC_REC_FEET + 3 * j;
-            w[0] = dt * (iw[r * 3 + 1] * ft[2] - iw[r * 3 + 2] * ft[1]);
-            w[1] = dt * (-iw[r * 3 + 0] * ft[2] + iw[r * 3 + 2] * ft[0]);
-            w[2] = dt * (iw[r * 3 + 0] * ft[1] - iw[r * 3 + 1] * ft[0]);
-        } else {
-            w[0] = w[1] = w[2] = 0.0;
-            w[r - 3] = dt / prm.mass;
-        }
-        double v = w[cc];
-        if constexpr (TERRAIN) {
-            const ldouble* Rj = S.tf + 9 * j;
-            v = w[0] * Rj[cc] + w[1] * Rj[3 + cc] + w[2] * Rj[6 + cc];
-        }
-        S.G0[e] = v;
+        const int r = e / 12;
+        S.G0[e] = g0_entry<TERRAIN>(prm, e, iw[r * 3 + 0], iw[r * 3 + 1], iw[r * 3 + 2], S.hdr, S.tf);
     }
     if (lane < 4) {
         const double r0 = prm.r[3 * lane], r1 = prm.r[3 * lane + 1], r2 = prm.r[3 * lane + 2];
         if constexpr (TERRAIN) {
-            const ldouble* R = S.tf + 9 * lane;
-            int e = 0;
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int b = a; b < 3; ++b)
-                    S.rb[6 * lane + e++] = r0 * R[a] * R[b] + r1 * R[3 + a] * R[3 + b] + r2 * R[6 + a] * R[6 + b];
+            rotated_weights(prm.r + 3 * lane, S.tf + 9 * lane, S.rb + 6 * lane);
         } else {
             S.rb[6 * lane + 0] = r0;
             S.rb[6 * lane + 1] = 0.0;

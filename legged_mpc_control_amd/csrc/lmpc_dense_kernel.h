@@ -12,6 +12,7 @@
 #include "lmpc/lmpc.h"
 #include "lmpc_device.h"
 #include "lmpc_kernel_common.h"
+#include "lmpc_qp_step.h"
 #include "lmpc_dense_common.h"
 
 #ifndef DSTAMP
@@ -199,17 +200,10 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
     }
     double f[3], s[5], z[5], is[5];  // is = 1/s, refreshed whenever s changes (used 4x per iteration)
     {
-        const double cnt = st ? (double)(S.fb[lk + 1] - S.fb[lk]) : 1.0;
-        f[0] = f[1] = 0.0;
-        f[2] = st ? fmin(0.5 * fzmax, prm.mass * prm.grav / cnt) : 0.0;
-        double o[5];
-        cons_resid(f, mu, fzmax, o);
+        const double cnt = st ? (double)(S.fb[lk + 1] - S.fb[lk]) : 1.0;  // stance legs of this leg-step's stage
+        ipm_start(st, cnt, prm.mass * prm.grav, mu, fzmax, f, s, is);  // is = 1/s: the centred z
 #pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            s[i] = st ? -o[i] : 1.0;
-            is[i] = 1.0 / s[i];
-            z[i] = LMPC_DENSE_Z0 * is[i];
-        }
+        for (int i = 0; i < 5; ++i) z[i] = LMPC_DENSE_Z0 * is[i];
     }
     double u[3] = {0.0, 0.0, 0.0}, rt[3] = {0.0, 0.0, 0.0};
     int qstatus = LMPC_QP_CONVERGED, ipm_it = 0, prounds = 0;
@@ -358,45 +352,27 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
         if (mode == PRED) {
             if (ipm_it >= prm.dense_iter_cap) break;  // test hook: hand the QP to the Riccati kernel
             double loc = 0.0;
-            if (st) {
-#pragma unroll
-                for (int i = 0; i < 5; ++i) loc += s[i] * z[i];
-            }
+            if (st) ipm_gap(s, z, loc);
             DSTAMP(2);
             sz = wave_sum(loc);
             mu_c = sz * imc;
             DSTAMP(12);  // complementarity mean (wave reduction)
             if (mu_c < tol || ipm_it >= it_end) {
-                act = 0;
-                if (st) {
-#pragma unroll
-                    for (int i = 0; i < 5; ++i)
-                        if (z[i] > LMPC_ACT_RATIO * s[i]) act |= 1 << i;
-                    const double fm = fmax(fabs(f[0]), fmax(fabs(f[1]), fabs(f[2])));
-                    if (fm < 1e-6 * fzmax) act = 15;
-                }
+                act = st ? ipm_guess_active(f, s, z, fzmax) : 0;
                 mode = POLISH;
                 rd = 0;
                 keep_tiles = 0;
                 have_base = false;
             } else {
-                double W[5] = {0, 0, 0, 0, 0}, wv[5] = {0, 0, 0, 0, 0};
+                const double rb0[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // R is inside H
+                double D[6];                                            // D = C'WC, packed
+                ipm_barrier<false>(st, s, is, z, mu, fzmax, rb0, D, rt);
                 if (st) {
-#pragma unroll
-                    for (int i = 0; i < 5; ++i) {
-                        W[i] = z[i] * is[i];
-                        wv[i] = W[i] * (s[i] - (i == 4 ? fzmax : 0.0));
-                    }
-                }
-                const double sx = W[0] + W[1], sy = W[2] + W[3];
-                if (st) {  // D = C'WC (R is inside H)
                     ldouble* bk = S.blk + 9 * lane;
-                    const double dxz = mu * (W[0] - W[1]), dyz = mu * (W[2] - W[3]), dzz = mu * mu * (sx + sy) + W[4];
-                    bk[0] = sx;  bk[1] = 0.0; bk[2] = dxz;
-                    bk[3] = 0.0; bk[4] = sy;  bk[5] = dyz;
-                    bk[6] = dxz; bk[7] = dyz; bk[8] = dzz;
+                    bk[0] = D[0]; bk[1] = D[1]; bk[2] = D[2];
+                    bk[3] = D[1]; bk[4] = D[3]; bk[5] = D[4];
+                    bk[6] = D[2]; bk[7] = D[4]; bk[8] = D[5];
                 }
-                cons_tw(wv, mu, rt);
             }
             DSTAMP(13);  // Newton-matrix blocks D and weights
         }
@@ -925,32 +901,13 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
 #pragma unroll
                 for (int m = 0; m < 3; ++m) S.lua[3 * lane + m] = u[m];
             }
-            if (st) {
-                double o[5];
-                cons_resid(u, mu, fzmax, o);
-#pragma unroll
-                for (int i = 0; i < 5; ++i) {
-                    dsa[i] = -o[i] - s[i];
-                    dza[i] = -z[i] - z[i] * is[i] * dsa[i];
-                    if (dsa[i] < 0.0) amax = fmin(amax, -s[i] * __builtin_amdgcn_rcp(dsa[i]));
-                    if (dza[i] < 0.0) amax = fmin(amax, -z[i] * __builtin_amdgcn_rcp(dza[i]));
-                }
-            }
+            if (st) ipm_pred_leg(u, s, is, z, mu, fzmax, dsa, dza, amax);
             const double aa = wave_min(amax);
             double loc = 0.0;
-            if (st) {
-#pragma unroll
-                for (int i = 0; i < 5; ++i) loc += (s[i] + aa * dsa[i]) * (z[i] + aa * dza[i]);
-            }
-            const double ratio = wave_sum(loc) / sz;  // = mu_aff / mu (the 1/mc factors cancel)
-            smu = ratio * ratio * ratio * mu_c;
-            if (st) {
-                double wv[5];
-#pragma unroll
-                for (int i = 0; i < 5; ++i)
-                    wv[i] = (z[i] * (s[i] - (i == 4 ? fzmax : 0.0)) + smu - dsa[i] * dza[i]) * is[i];
-                cons_tw(wv, mu, rt);
-            }
+            if (st) ipm_aff_gap(s, z, dsa, dza, aa, loc);
+            // ratio = mu_aff / mu over the sums, not the means as in the Riccati kernels: the 1/mc factors cancel
+            smu = ipm_centring(wave_sum(loc) / sz, mu_c);
+            if (st) ipm_corr_rhs(s, is, z, dsa, dza, smu, mu, fzmax, rt);
             mode = CORR;
             DSTAMP(8);  // predictor step length + corrector terms
         } else if (mode == CORR) {
@@ -959,23 +916,13 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
 #pragma unroll
             for (int i = 0; i < 5; ++i) ds[i] = dz[i] = 0.0;
             if (st) {
-                double o[5], oa[5], ua[3];
+                double ua[3];
 #pragma unroll
                 for (int m = 0; m < 3; ++m) ua[m] = S.lua[3 * lane + m];
-                cons_resid(u, mu, fzmax, o);
-                cons_resid(ua, mu, fzmax, oa);
-#pragma unroll
-                for (int i = 0; i < 5; ++i) {
-                    const double dsa = -oa[i] - s[i];
-                    const double dza = -z[i] - z[i] * is[i] * dsa;
-                    ds[i] = -o[i] - s[i];
-                    dz[i] = (smu - z[i] * s[i] - dsa * dza - z[i] * ds[i]) * is[i];
-                    if (ds[i] < 0.0) amax = fmin(amax, -s[i] * __builtin_amdgcn_rcp(ds[i]));
-                    if (dz[i] < 0.0) dmax = fmin(dmax, -z[i] * __builtin_amdgcn_rcp(dz[i]));
-                }
+                ipm_corr_leg(u, ua, s, is, z, smu, mu, fzmax, ds, dz, amax, dmax);
             }
-            const double alpha = fmin(1.0, LMPC_STEP_FRAC * wave_min(amax));
-            const double alpd = fmin(1.0, LMPC_STEP_FRAC * wave_min(dmax));
+            const double alpha = ipm_step_length(wave_min(amax));
+            const double alpd = ipm_step_length(wave_min(dmax));
             if (st) {
 #pragma unroll
                 for (int m = 0; m < 3; ++m) f[m] += alpha * (u[m] - f[m]);
@@ -1013,34 +960,12 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
             }
             const double gscale = wave_max(gloc);
             int changed = 0;
-            double sres = 0.0;  // stationarity residual on the leg-step's free directions (lmpc_kernel_common.h)
+            double sres = 0.0;  // stationarity residual on the leg-step's free directions (leg_certify)
             if (st) {
-                double o[5];
-                cons_resid(u, mu, fzmax, o);
-                int imax = -1;
-                double vmax = prm.tol_p * fzmax;
-#pragma unroll
-                for (int i = 0; i < 5; ++i)
-                    if (!((act >> i) & 1) && o[i] > vmax) {
-                        vmax = o[i];
-                        imax = i;
-                    }
-                if (imax >= 0) {
-                    act |= 1 << imax;
-                    changed = 1;
-                } else if (apex) {  // the cone test is the whole certificate at the apex
-                    if (g[2] / mu < fabs(g[0]) + fabs(g[1]) - prm.tol_d * gscale) {
-                        act = (g[0] < 0.0 ? 2 : 1) | (g[1] < 0.0 ? 8 : 4);
-                        changed = 1;
-                    }
-                } else {  // (act = 0: no multipliers, the residual is g itself)
-                    const LegKkt kk = leg_kkt(act, g, mu, -prm.tol_d * gscale);
-                    if (kk.drop >= 0) {
-                        act &= ~(1 << kk.drop);
-                        changed = 1;
-                    }
-                    sres = kk.res;
-                }
+                const LegCert c = leg_certify(u, g, act, apex, mu, fzmax, prm.tol_p * fzmax, prm.tol_d * gscale);
+                act = c.act;
+                changed = c.changed ? 1 : 0;
+                sres = c.res;
             }
             DSTAMP(10);  // polish verification
             const unsigned long long chg = __ballot(changed);
@@ -1174,18 +1099,9 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
                         }
                         const double gs2 = wave_max(gl2);
                         bool ok = !bad2;
-                        if (st) {
-                            double o[5];
-                            cons_resid(ur, mu, fzmax, o);
-#pragma unroll
-                            for (int i = 0; i < 5; ++i)
-                                if (!((act >> i) & 1) && o[i] > prm.tol_p * fzmax) ok = false;
-                            if (apex) {
-                                ok = ok && !(g2[2] / mu < fabs(g2[0]) + fabs(g2[1]) - prm.tol_d * gs2);
-                            } else {
-                                const LegKkt kk = leg_kkt(act, g2, mu, -prm.tol_d * gs2);
-                                ok = ok && kk.drop < 0 && kk.res <= prm.tol_d * gs2;
-                            }
+                        if (st) {  // the certificate asks nothing of the leg-step, and its residual is within tol_d
+                            const LegCert c = leg_certify(ur, g2, act, apex, mu, fzmax, prm.tol_p * fzmax, prm.tol_d * gs2);
+                            ok = ok && !c.changed && c.res <= prm.tol_d * gs2;
                         }
 #ifdef LMPC_REFINE_DIAG
                         {
@@ -1223,9 +1139,7 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
             if (++rd >= prm.max_rounds) {
                 keep_tiles = 0;
                 schur = false;  // the interior point resumes: its own right-hand sides and factorisations
-                if (++att >= prm.max_attempts) break;
-                tol = retry_tol(tol, att);
-                it_end += prm.max_iter;
+                if (!ipm_retry(prm, att, tol, it_end)) break;
                 mode = PRED;
             }
         }
@@ -1257,12 +1171,8 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
     // ---- output: stance forces through LDS to the lane of leg-step 4k + j ----
     LMPC_SYNC();
     if (st) {
-        double fo[3] = {u[0], u[1], u[2]};
-        if constexpr (TERRAIN) {
-            const ldouble* Rj = S.tf + 9 * lj;
-#pragma unroll
-            for (int p = 0; p < 3; ++p) fo[p] = Rj[3 * p] * u[0] + Rj[3 * p + 1] * u[1] + Rj[3 * p + 2] * u[2];
-        }
+        double fo[3];
+        world_force<TERRAIN>(S.tf + 9 * lj, u, fo);
 #pragma unroll
         for (int p = 0; p < 3; ++p) S.vec[3 * lane + p] = fo[p];
     }
@@ -1272,10 +1182,7 @@ __device__ __forceinline__ bool dense_body(const DevParams prm, const double* __
 #pragma unroll
         for (int p = 0; p < 3; ++p) gout[3 * lane + p] = (anybad || !stl) ? 0.0 : S.vec[3 * (stl ? rank : 0) + p];
     }
-    if (lane == 0) {
-        if (status) status[qp] = anybad ? LMPC_QP_NAN : qstatus;
-        if (iters) iters[qp] = ipm_it | (prounds << 16);
-    }
+    qp_store_words(status, iters, qp, lane, anybad, qstatus, ipm_it, prounds);
     DSTAMP(2);
     DSTAMP_FLUSH(qp);
     return true;

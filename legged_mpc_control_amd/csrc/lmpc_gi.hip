@@ -31,6 +31,7 @@
 #include "lmpc_dense_common.h"
 #include "lmpc_device.h"
 #include "lmpc_kernel_common.h"
+#include "lmpc_qp_step.h"
 
 namespace lmpc {
 
@@ -632,17 +633,12 @@ __global__ void __launch_bounds__(64) lmpc_gi_kernel(const DevParams prm, const 
         double sres = 0.0;
         bool fail = false;
         if (lane < nls) {
-            double o[5];
-            cons_resid(u, mu, fzmax, o);
-#pragma unroll
-            for (int i = 0; i < 5; ++i) fail |= o[i] > prm.tol_p * fzmax;
-            if ((lact & 3) == 3 || (lact & 12) == 12) {  // apex (f = 0): the cone test
-                fail |= g[2] / mu < fabs(g[0]) + fabs(g[1]) - prm.tol_d * gscale;
-            } else {
-                const LegKkt kk = leg_kkt(lact, g, mu, -prm.tol_d * gscale);
-                fail |= kk.drop >= 0;
-                sres = kk.res;
-            }
+            // whatever the certificate asks for is a failure here; every face is held to feasibility, the active too
+            fail |= leg_violated(u, 0, mu, fzmax, prm.tol_p * fzmax) >= 0;
+            const bool apex = (lact & 3) == 3 || (lact & 12) == 12;  // f = 0
+            const LegCert c = leg_certify_dual(g, lact, apex, mu, prm.tol_d * gscale);
+            fail |= c.changed;
+            sres = c.res;
         }
         const double sr = wave_max(sres);
 #ifdef LMPC_KKT_DIAG
@@ -667,16 +663,8 @@ __global__ void __launch_bounds__(64) lmpc_gi_kernel(const DevParams prm, const 
     LMPC_SYNC();
     double fo[3] = {0.0, 0.0, 0.0};
     if (lane < nls) {
-        const double u0 = S.vec[lv0], u1 = S.vec[lv0 + 1], u2 = S.vec[lv0 + 2];
-        fo[0] = u0;
-        fo[1] = u1;
-        fo[2] = u2;
-        if constexpr (TERRAIN) {
-            const int lj = S.lsm[lane] & 3;
-            const ldouble* Rj = S.tf + 9 * lj;
-#pragma unroll
-            for (int pp = 0; pp < 3; ++pp) fo[pp] = Rj[3 * pp] * u0 + Rj[3 * pp + 1] * u1 + Rj[3 * pp + 2] * u2;
-        }
+        const double u[3] = {S.vec[lv0], S.vec[lv0 + 1], S.vec[lv0 + 2]};
+        world_force<TERRAIN>(S.tf + 9 * (S.lsm[lane] & 3), u, fo);
     }
     LMPC_SYNC();
     if (lane < nls) {

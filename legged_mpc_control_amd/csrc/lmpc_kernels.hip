@@ -40,6 +40,7 @@
 #include "lmpc/lmpc.h"
 #include "lmpc_device.h"
 #include "lmpc_kernel_common.h"
+#include "lmpc_qp_step.h"
 
 namespace lmpc {
 
@@ -927,12 +928,7 @@ __global__ void __launch_bounds__(64, WPE) lmpc_qp_kernel(const DevParams prm, c
     if (qp >= batch) return;
     const int lane = threadIdx.x;
     const int H = prm.H;
-    if (prm.dense) {  // QPs with 1..DENSE_MAX_LS stance leg-steps went to a dense-path kernel (H <= 16 here)
-        const bool stl = lane < 4 * H && contact[(size_t)qp * 4 * H + lane] != 0;
-        const int n = __popcll(__ballot(stl));
-        // the GI kernel flags the QPs it solved; the ones it left (step cap, non-finite step) are solved here
-        if (n >= 1 && n <= DENSE_MAX_LS && (!dense_done || dense_done[qp])) return;
-    }
+    if (dense_took(prm, contact, dense_done, qp, H, lane)) return;
     const int RL = 33 + 12 * H;
     Smem S = carve(lmpc_smem, H);
     ldouble* const tf = S.st + SK * H;  // TERRAIN only: R_j (9 each, row-major) | R_j' diag(r_j) R_j packed (6 each)
@@ -945,57 +941,21 @@ __global__ void __launch_bounds__(64, WPE) lmpc_qp_kernel(const DevParams prm, c
     if (lane < 33) S.hdr[lane] = rin[lane];
     S.xr = (const gdouble*)(rin + 33);
     if constexpr (TERRAIN) {
-        if (lane < 4) {
-            // contact frame of leg `lane` (same closed form as lmpc_terrain_frame, lmpc_host.cpp)
-            const double* nin = normals + (size_t)qp * 12 + 3 * lane;
-            const double n0 = nin[0], n1 = nin[1], n2 = nin[2];
-            const double nn = sqrt(n0 * n0 + n1 * n1 + n2 * n2);
-            const double nx = n0 / nn, ny = n1 / nn, c = n2 / nn;
-            const double h = 1.0 / (1.0 + c);
-            const double R[9] = {1.0 - nx * nx * h, -nx * ny * h, nx, -nx * ny * h, 1.0 - ny * ny * h, ny, -nx, -ny, c};
+        if (lane < 4) {  // contact frame of leg `lane`
+            double R[9];
+            terrain_frame(normals + (size_t)qp * 12 + 3 * lane, R);
 #pragma unroll
             for (int e = 0; e < 9; ++e) tf[9 * lane + e] = R[e];
-            const double r0 = prm.r[3 * lane], r1 = prm.r[3 * lane + 1], r2 = prm.r[3 * lane + 2];
-            int e = 0;
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int b = a; b < 3; ++b)  // packed [xx xy xz yy yz zz]
-                    tf[36 + 6 * lane + e++] = r0 * R[a] * R[b] + r1 * R[3 + a] * R[3 + b] + r2 * R[6 + a] * R[6 + b];
+            rotated_weights(prm.r + 3 * lane, R, tf + 36 + 6 * lane);
         }
     }
     LMPC_SYNC();
     double iw[9];  // (R I_b R')^-1, computed redundantly by every lane
-    {
-        const ldouble* R = S.hdr + LMPC_REC_ROT;
-        double RI[9], Iw[9];
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j)
-                RI[i * 3 + j] = R[i * 3 + 0] * prm.Ib[0 * 3 + j] + R[i * 3 + 1] * prm.Ib[1 * 3 + j] + R[i * 3 + 2] * prm.Ib[2 * 3 + j];
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j)
-                Iw[i * 3 + j] = RI[i * 3 + 0] * R[j * 3 + 0] + RI[i * 3 + 1] * R[j * 3 + 1] + RI[i * 3 + 2] * R[j * 3 + 2];
-        const double c00 = Iw[4] * Iw[8] - Iw[5] * Iw[7];
-        const double c01 = Iw[5] * Iw[6] - Iw[3] * Iw[8];
-        const double c02 = Iw[3] * Iw[7] - Iw[4] * Iw[6];
-        const double id = 1.0 / (Iw[0] * c00 + Iw[1] * c01 + Iw[2] * c02);
-        iw[0] = c00 * id;
-        iw[1] = (Iw[2] * Iw[7] - Iw[1] * Iw[8]) * id;
-        iw[2] = (Iw[1] * Iw[5] - Iw[2] * Iw[4]) * id;
-        iw[3] = c01 * id;
-        iw[4] = (Iw[0] * Iw[8] - Iw[2] * Iw[6]) * id;
-        iw[5] = (Iw[2] * Iw[3] - Iw[0] * Iw[5]) * id;
-        iw[6] = c02 * id;
-        iw[7] = (Iw[1] * Iw[6] - Iw[0] * Iw[7]) * id;
-        iw[8] = (Iw[0] * Iw[4] - Iw[1] * Iw[3]) * id;
-    }
-    for (int k = lane; k < H; k += 64) {
-        double sn, cn;
-        sincos(S.xr[12 * k + 2], &sn, &cn);
-        S.cs[2 * k] = cn;
-        S.cs[2 * k + 1] = sn;
-    }
-    // G0 = dt [I_w^-1 skew(r_j) ; I/m]  (Utils::skew, Utils.cpp:89-95)
+    world_inertia_inv(S.hdr + LMPC_REC_ROT, prm.Ib, iw);
+    yaw_cos_sin(S.xr, S.cs, H, lane);
+    // G0 = dt [I_w^-1 skew(r_j) ; I/m]  (Utils::skew, Utils.cpp:89-95).  Not g0_entry: this kernel forms the flat entry
+    // from the skew column and the terrain's mass rows without the zero terms, and is compiled without the other
+    // kernels' floating-point flags, so their expression would not give its bits
     for (int e = lane; e < 72; e += 64) {
         const int r = e / 12, c = e % 12, j = c / 3, cc = c % 3;
         double v;
@@ -1047,22 +1007,8 @@ __global__ void __launch_bounds__(64, WPE) lmpc_qp_kernel(const DevParams prm, c
         lsj[t] = ls & 3;
         st[t] = valid[t] && contact[(size_t)qp * 4 * H + ls] != 0;
         nst_loc += st[t] ? 1 : 0;
-        f[t][0] = f[t][1] = 0.0;
-        {
-            // starting point: each stance leg carries its share of the weight (fz = m g / n_stance,
-            // capped at fmax/2), zero tangential force; slacks from the constraints and a
-            // centred z = 1/s (s z = 1).  Measured: ~0.9 fewer interior-point iterations on
-            // average than fz = fmax/2, z = 1 (tools/variant_sweep.py, profiles/r01_init_sweep.log).
-            const double cnt = quad_sum(st[t] ? 1.0 : 0.0);  // stance legs of this stage (all lanes: DPP)
-            f[t][2] = st[t] ? fmin(0.5 * fzmax, prm.mass * prm.grav / fmax(cnt, 1.0)) : 0.0;
-        }
-        double o[5];
-        cons_resid(f[t], mu, fzmax, o);
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            s[t][i] = st[t] ? -o[i] : 1.0;
-            z[t][i] = 1.0 / s[t][i];
-        }
+        const double cnt = quad_sum(st[t] ? 1.0 : 0.0);  // stance legs of this stage (all lanes: DPP)
+        ipm_start(st[t], fmax(cnt, 1.0), prm.mass * prm.grav, mu, fzmax, f[t], s[t], z[t]);
         u[t][0] = u[t][1] = u[t][2] = 0.0;
     }
     const double nst = wave_sum((double)nst_loc);
@@ -1103,56 +1049,20 @@ __global__ void __launch_bounds__(64, WPE) lmpc_qp_kernel(const DevParams prm, c
                 double loc = 0.0;
 #pragma unroll
                 for (int t = 0; t < LS; ++t)
-                    if (st[t])
-#pragma unroll
-                        for (int i = 0; i < 5; ++i) loc += s[t][i] * z[t][i];
+                    if (st[t]) ipm_gap(s[t], z[t], loc);
                 mu_c = wave_sum(loc) / mc;
                 if (mu_c < tol || ipm_it >= it_end) {
-                    // active set from the interior point: z > LMPC_ACT_RATIO s, lift-off legs -> apex
 #pragma unroll
-                    for (int t = 0; t < LS; ++t) {
-                        act[t] = 0;
-                        if (!st[t]) continue;
-#pragma unroll
-                        for (int i = 0; i < 5; ++i)
-                            if (z[t][i] > LMPC_ACT_RATIO * s[t][i]) act[t] |= 1 << i;
-                        const double fm = fmax(fabs(f[t][0]), fmax(fabs(f[t][1]), fabs(f[t][2])));
-                        if (fm < 1e-6 * fzmax) act[t] = 15;
-                    }
+                    for (int t = 0; t < LS; ++t) act[t] = st[t] ? ipm_guess_active(f[t], s[t], z[t], fzmax) : 0;
                     mode = POLISH;
                     rd = 0;
                 } else {
                     // stage data: Rt = diag(r) + C'WC, rt = C'(W(s-b)), T = I (stance) / 0 (swing), up = 0
 #pragma unroll
                     for (int t = 0; t < LS; ++t) {
-                        double W[5] = {0, 0, 0, 0, 0}, wv[5] = {0, 0, 0, 0, 0};
-                        if (st[t]) {
-#pragma unroll
-                            for (int i = 0; i < 5; ++i) {
-                                W[i] = z[t][i] * rcp_nr(s[t][i]);  // 1/s is recomputed where needed: keeping it
-                                                                    // live across the factor/solve calls spills it
-                                wv[i] = W[i] * (s[t][i] - (i == 4 ? fzmax : 0.0));
-                            }
-                        }
-                        const double sx = W[0] + W[1], sy = W[2] + W[3];
-                        const int j = lsj[t];
-                        if constexpr (!TERRAIN) {
-                            Rt[t][0] = prm.r[3 * j + 0] + sx;
-                            Rt[t][1] = 0.0;
-                            Rt[t][2] = mu * (W[0] - W[1]);
-                            Rt[t][3] = prm.r[3 * j + 1] + sy;
-                            Rt[t][4] = mu * (W[2] - W[3]);
-                            Rt[t][5] = prm.r[3 * j + 2] + mu * mu * (sx + sy) + W[4];
-                        } else {
-                            const ldouble* rb = tf + 36 + 6 * j;
-                            Rt[t][0] = rb[0] + sx;
-                            Rt[t][1] = rb[1];
-                            Rt[t][2] = rb[2] + mu * (W[0] - W[1]);
-                            Rt[t][3] = rb[3] + sy;
-                            Rt[t][4] = rb[4] + mu * (W[2] - W[3]);
-                            Rt[t][5] = rb[5] + mu * mu * (sx + sy) + W[4];
-                        }
-                        cons_tw(wv, mu, rt[t]);
+                        const RecipOf is{s[t]};  // recomputed where read: kept across the factor/solve calls it spills
+                        if constexpr (!TERRAIN) ipm_barrier<true>(st[t], s[t], is, z[t], mu, fzmax, prm.r + 3 * lsj[t], Rt[t], rt[t]);
+                        else ipm_barrier<false>(st[t], s[t], is, z[t], mu, fzmax, tf + 36 + 6 * lsj[t], Rt[t], rt[t]);
                     }
                 }
             }
@@ -1215,35 +1125,20 @@ __global__ void __launch_bounds__(64, WPE) lmpc_qp_kernel(const DevParams prm, c
 #pragma unroll
                     for (int m = 0; m < 3; ++m) ua[t][m] = u[t][m];
                     if (!st[t]) continue;
-                    double o[5];
-                    cons_resid(u[t], mu, fzmax, o);
-#pragma unroll
-                    for (int i = 0; i < 5; ++i) {
-                        dsa[t][i] = -o[i] - s[t][i];
-                        dza[t][i] = -z[t][i] - z[t][i] * rcp_nr(s[t][i]) * dsa[t][i];
-                        // fraction to the boundary: the hardware reciprocal estimate is ample here
-                        if (dsa[t][i] < 0.0) amax = fmin(amax, -s[t][i] * __builtin_amdgcn_rcp(dsa[t][i]));
-                        if (dza[t][i] < 0.0) amax = fmin(amax, -z[t][i] * __builtin_amdgcn_rcp(dza[t][i]));
-                    }
+                    const RecipOf is{s[t]};
+                    ipm_pred_leg(u[t], s[t], is, z[t], mu, fzmax, dsa[t], dza[t], amax);
                 }
                 const double aa = wave_min(amax);
                 double loc = 0.0;
 #pragma unroll
                 for (int t = 0; t < LS; ++t)
-                    if (st[t])
-#pragma unroll
-                        for (int i = 0; i < 5; ++i) loc += (s[t][i] + aa * dsa[t][i]) * (z[t][i] + aa * dza[t][i]);
-                const double ratio = (wave_sum(loc) / mc) / mu_c;
-                smu = ratio * ratio * ratio * mu_c;
-                // corrector right-hand side
+                    if (st[t]) ipm_aff_gap(s[t], z[t], dsa[t], dza[t], aa, loc);
+                smu = ipm_centring((wave_sum(loc) / mc) / mu_c, mu_c);
 #pragma unroll
                 for (int t = 0; t < LS; ++t) {
                     if (!st[t]) continue;
-                    double wv[5];
-#pragma unroll
-                    for (int i = 0; i < 5; ++i)
-                        wv[i] = (z[t][i] * (s[t][i] - (i == 4 ? fzmax : 0.0)) + smu - dsa[t][i] * dza[t][i]) * rcp_nr(s[t][i]);
-                    cons_tw(wv, mu, rt[t]);
+                    const RecipOf is{s[t]};
+                    ipm_corr_rhs(s[t], is, z[t], dsa[t], dza[t], smu, mu, fzmax, rt[t]);
                 }
                 mode = CORR;
                 SUB(17);  // (diagnostic) predictor post-step
@@ -1255,24 +1150,13 @@ __global__ void __launch_bounds__(64, WPE) lmpc_qp_kernel(const DevParams prm, c
 #pragma unroll
                     for (int i = 0; i < 5; ++i) ds[t][i] = dz[t][i] = 0.0;
                     if (!st[t]) continue;
-                    double o[5], oa[5];
-                    cons_resid(u[t], mu, fzmax, o);
-                    cons_resid(ua[t], mu, fzmax, oa);
-#pragma unroll
-                    for (int i = 0; i < 5; ++i) {
-                        const double is = rcp_nr(s[t][i]);
-                        const double dsa = -oa[i] - s[t][i];  // predictor step, recomputed from u_aff
-                        const double dza = -z[t][i] - z[t][i] * is * dsa;
-                        ds[t][i] = -o[i] - s[t][i];
-                        dz[t][i] = (smu - z[t][i] * s[t][i] - dsa * dza - z[t][i] * ds[t][i]) * is;
-                        if (ds[t][i] < 0.0) amax = fmin(amax, -s[t][i] * __builtin_amdgcn_rcp(ds[t][i]));
-                        if (dz[t][i] < 0.0) dmax = fmin(dmax, -z[t][i] * __builtin_amdgcn_rcp(dz[t][i]));
-                    }
+                    const RecipOf is{s[t]};
+                    ipm_corr_leg(u[t], ua[t], s[t], is, z[t], smu, mu, fzmax, ds[t], dz[t], amax, dmax);
                 }
-                const double alpha = fmin(1.0, LMPC_STEP_FRAC * wave_min(amax));
-                const double alpd = fmin(1.0, LMPC_STEP_FRAC * wave_min(dmax));
+                const double alpha = ipm_step_length(wave_min(amax));
+                const double alpd = ipm_step_length(wave_min(dmax));
 #pragma unroll
-                for (int t = 0; t < LS; ++t) {
+                for (int t = 0; t < LS; ++t) {  // (not a shared function: as one, the two-leg-step instances spill more)
                     if (!st[t]) continue;
 #pragma unroll
                     for (int m = 0; m < 3; ++m) f[t][m] += alpha * (u[t][m] - f[t][m]);
@@ -1286,7 +1170,7 @@ __global__ void __launch_bounds__(64, WPE) lmpc_qp_kernel(const DevParams prm, c
                 mode = PRED;
                 SUB(18);  // (diagnostic) corrector post-step
             } else {
-                // ---- polish verification, a KKT certificate independent of the factorisation (lmpc_lq.hip): the
+                // ---- polish verification, a KKT certificate independent of the factorisation (leg_certify): the
                 // trajectory is the dynamics of the forces returned, the adjoint of that trajectory gives the
                 // gradient, every stance leg-step is primal feasible, stationary on its free directions and carries
                 // multipliers of the right sign ----
@@ -1334,25 +1218,9 @@ __global__ void __launch_bounds__(64, WPE) lmpc_qp_kernel(const DevParams prm, c
                     g[t][0] = g[t][1] = g[t][2] = 0.0;
                     if (!valid[t]) continue;
                     const int k = lsk[t], j = lsj[t];
-                    const ldouble* lam = S.st + k * SK + SO_LAM;
-                    double ru[3];  // input-Hessian block times u
-                    if constexpr (!TERRAIN) {
-#pragma unroll
-                        for (int p = 0; p < 3; ++p) ru[p] = prm.r[3 * j + p] * u[t][p];
-                    } else {
-                        const ldouble* rb = tf + 36 + 6 * j;
-                        ru[0] = rb[0] * u[t][0] + rb[1] * u[t][1] + rb[2] * u[t][2];
-                        ru[1] = rb[1] * u[t][0] + rb[3] * u[t][1] + rb[4] * u[t][2];
-                        ru[2] = rb[2] * u[t][0] + rb[4] * u[t][1] + rb[5] * u[t][2];
-                    }
-#pragma unroll
-                    for (int p = 0; p < 3; ++p) {
-                        double v = ru[p];
-#pragma unroll
-                        for (int m = 0; m < 6; ++m) v += S.G0[m * 12 + 3 * j + p] * lam[6 + m];
-                        g[t][p] = v;
-                        gloc = fmax(gloc, fabs(v));
-                    }
+                    const ldouble* lam = S.st + k * SK + SO_LAM + 6;
+                    if constexpr (!TERRAIN) leg_gradient<true>(prm.r + 3 * j, u[t], S.G0, j, lam, g[t], gloc);
+                    else leg_gradient<false>(tf + 36 + 6 * j, u[t], S.G0, j, lam, g[t], gloc);
                 }
                 const double gscale = wave_max(gloc);
                 int changed = 0;
@@ -1360,21 +1228,13 @@ __global__ void __launch_bounds__(64, WPE) lmpc_qp_kernel(const DevParams prm, c
 #pragma unroll
                 for (int t = 0; t < LS; ++t) {
                     if (!st[t]) continue;
-                    double o[5];
-                    cons_resid(u[t], mu, fzmax, o);
-                    int imax = -1;
-                    double vmax = prm.tol_p * fzmax;
-#pragma unroll
-                    for (int i = 0; i < 5; ++i)
-                        if (!((act[t] >> i) & 1) && o[i] > vmax) {
-                            vmax = o[i];
-                            imax = i;
-                        }
-                    if (imax >= 0) {
+                    const int imax = leg_violated(u[t], act[t], mu, fzmax, prm.tol_p * fzmax);
+                    if (imax >= 0) {  // a violated face enters first, the most violated one
                         act[t] |= 1 << imax;
                         changed = 1;
                         continue;
                     }
+                    // (the text of leg_certify_dual: through the function the <1,false,2> instance spills 6 more VGPRs)
                     if (apex[t]) {  // the cone test is the whole certificate at the apex
                         if (g[t][2] / mu < fabs(g[t][0]) + fabs(g[t][1]) - prm.tol_d * gscale) {
                             act[t] = (g[t][0] < 0.0 ? 2 : 1) | (g[t][1] < 0.0 ? 8 : 4);
@@ -1413,9 +1273,7 @@ __global__ void __launch_bounds__(64, WPE) lmpc_qp_kernel(const DevParams prm, c
                         continue;
                     }
                     // retry: tighter interior point, then a fresh polish
-                    if (++att >= prm.max_attempts) break;
-                    tol = retry_tol(tol, att);
-                    it_end += prm.max_iter;
+                    if (!ipm_retry(prm, att, tol, it_end)) break;
                     mode = PRED;
                 }
             }
@@ -1434,26 +1292,7 @@ __global__ void __launch_bounds__(64, WPE) lmpc_qp_kernel(const DevParams prm, c
         }
     }
     STAMP(1);
-    // ---- NaN guard (reference: NaN -> zeros, ConvexQPSolver.cpp:321-326) and output ----
-    int bad = 0;
-#pragma unroll
-    for (int t = 0; t < LS; ++t)
-        if (valid[t]) bad |= (u[t][0] != u[t][0] || u[t][1] != u[t][1] || u[t][2] != u[t][2]) ? 1 : 0;
-    const bool anybad = __any(bad);
-    double* gout = grf + (size_t)qp * 12 * H;
-#pragma unroll
-    for (int t = 0; t < LS; ++t) {
-        if (!valid[t]) continue;
-        const int ls = lane + 64 * t;
-        double fo[3] = {u[t][0], u[t][1], u[t][2]};
-        if constexpr (TERRAIN) {  // f = R_j g (world frame)
-            const ldouble* Rj = tf + 9 * lsj[t];
-#pragma unroll
-            for (int p = 0; p < 3; ++p) fo[p] = Rj[3 * p] * u[t][0] + Rj[3 * p + 1] * u[t][1] + Rj[3 * p + 2] * u[t][2];
-        }
-#pragma unroll
-        for (int p = 0; p < 3; ++p) gout[3 * ls + p] = (anybad || !st[t]) ? 0.0 : fo[p];
-    }
+    const bool anybad = qp_store_forces<LS, TERRAIN>(valid, st, lsj, u, tf, grf + (size_t)qp * 12 * H, lane);
     STAMP(5);  // epilogue
     STAMP_FLUSH(qp);
     if (prm.act_out) {
@@ -1461,10 +1300,7 @@ __global__ void __launch_bounds__(64, WPE) lmpc_qp_kernel(const DevParams prm, c
         for (int t = 0; t < LS; ++t)
             if (valid[t]) prm.act_out[(size_t)qp * 4 * H + lane + 64 * t] = (uint8_t)(anybad ? 0 : act_fin[t]);
     }
-    if (lane == 0) {
-        if (status) status[qp] = anybad ? LMPC_QP_NAN : qstatus;
-        if (iters) iters[qp] = ipm_it | (prounds << 16);
-    }
+    qp_store_words(status, iters, qp, lane, anybad, qstatus, ipm_it, prounds);
 }
 
 #define LMPC_INST(LS_, T_, W_)                                                                                         \

@@ -4,7 +4,7 @@
 // One 64-lane wavefront per QP, no global scratch and no outlined calls: the per-stage factors the vector passes
 // need are kept in a 135-double LDS slot per stage (14.4 KB per QP at H = 10: eight QPs -- two waves per SIMD --
 // share a CU; 36 KB at H = 30: four), and everything else lives in registers.  The QP, the interior point and the
-// polish are those of lmpc_kernels.hip (ConvexQPSolver.cpp:16-346 restated); what changes is how the
+// polish are lmpc_qp_step.h's (ConvexQPSolver.cpp:16-346 restated); what changes is how the
 // Newton systems are solved (numpy replica step for step: tools/lq_proto.py, RED6=1):
 //
 //   reduced inputs (interior point): a stage's 12 inputs reach the dynamics only through f = Bt u (rows 6-11), so
@@ -29,7 +29,7 @@
 //   corrector          the new rr changes g only: rho = dg - K P22 dg (parallel; P22 recovered from Z), then the
 //                      backward sweep p_k = q_k + A'y - Z'(K za + rho), y = p + v, za = y[6:12], the forward sweep
 //                      and the inputs as above
-//   polish check       the adjoint lambda from the trajectory (independent of the factorisation), as lmpc_kernels.hip
+//   polish check       the adjoint lambda from the trajectory (independent of the factorisation), then leg_certify_dual
 //
 // The stage-k operands of the factorisation come from LDS (U or Bt in the Z field, rr in the x field, dv, written
 // before it) and, in the polish, from the leg-step lanes' registers (Rr_j, by readlane: wave-uniform per stage and
@@ -47,6 +47,7 @@
 #include "lmpc/lmpc.h"
 #include "lmpc_device.h"
 #include "lmpc_kernel_common.h"
+#include "lmpc_qp_step.h"
 
 #ifndef LQ_STAMP
 #define LQ_MARK(v) do {} while (0)
@@ -187,7 +188,7 @@ __device__ __forceinline__ void sym3_solve(const double R[6], const double b[3],
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// The kernel.  LS = leg-steps per lane (ceil(4H/64)); TERRAIN: per-leg contact frames (lmpc_kernels.hip).
+// The kernel.  LS = leg-steps per lane (ceil(4H/64)); TERRAIN: per-leg contact frames (terrain_frame).
 // WPE = waves per SIMD the register budget allows: 2 (256 registers, LS = 1 only: eight QPs per CU at H <= 10) or 1
 // (512, no spills: the instance for batches of at most one QP per SIMD, and for LS = 2).
 // ---------------------------------------------------------------------------------------------------------
@@ -204,11 +205,7 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
     if (qp >= batch) return;
     const int lane = threadIdx.x;
     const int H = prm.H;
-    if (prm.dense && !after_dense) {  // QPs with 1..DENSE_MAX_LS stance leg-steps went to a dense-path kernel (H <= 16 here)
-        const bool stl = lane < 4 * H && contact[(size_t)qp * 4 * H + lane] != 0;
-        const int n = __popcll(__ballot(stl));
-        if (n >= 1 && n <= DENSE_MAX_LS && (!dense_done || dense_done[qp])) return;
-    }
+    if (!after_dense && dense_took(prm, contact, dense_done, qp, H, lane)) return;
     ldouble* const sm = (ldouble*)lq_smem;
     ldouble* const hdr = sm + LQF_HDR;
     ldouble* const G0s = sm + LQF_G0;
@@ -242,80 +239,30 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
     if (lane < 4) zero[lane] = 0.0;
     if constexpr (TERRAIN) {
         if (lane < 4) {
-            const double* nin = normals + (size_t)qp * 12 + 3 * lane;
-            const double n0 = nin[0], n1 = nin[1], n2 = nin[2];
-            const double nn = sqrt(n0 * n0 + n1 * n1 + n2 * n2);
-            const double nx = n0 / nn, ny = n1 / nn, c = n2 / nn;
-            const double h = 1.0 / (1.0 + c);
-            const double R[9] = {1.0 - nx * nx * h, -nx * ny * h, nx, -nx * ny * h, 1.0 - ny * ny * h, ny, -nx, -ny, c};
+            double R[9];
+            terrain_frame(normals + (size_t)qp * 12 + 3 * lane, R);
 #pragma unroll
             for (int e = 0; e < 9; ++e) tf[9 * lane + e] = R[e];
-            const double r0 = prm.r[3 * lane], r1 = prm.r[3 * lane + 1], r2 = prm.r[3 * lane + 2];
-            int e = 0;
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int b = a; b < 3; ++b) rbt[6 * lane + e++] = r0 * R[a] * R[b] + r1 * R[3 + a] * R[3 + b] + r2 * R[6 + a] * R[6 + b];
+            rotated_weights(prm.r + 3 * lane, R, rbt + 6 * lane);
         }
     }
-    for (int k = lane; k < H; k += 64) {
-        double sn, cn;
-        sincos(xr[12 * k + 2], &sn, &cn);
-        cs[2 * k] = cn;
-        cs[2 * k + 1] = sn;
-    }
+    yaw_cos_sin(xr, cs, H, lane);
     LMPC_SYNC();
     {
         double iw[9];
-        const ldouble* R = hdr + LMPC_REC_ROT;
-        double RI[9], Iw[9];
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j)
-                RI[i * 3 + j] = R[i * 3 + 0] * prm.Ib[0 * 3 + j] + R[i * 3 + 1] * prm.Ib[1 * 3 + j] + R[i * 3 + 2] * prm.Ib[2 * 3 + j];
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j)
-                Iw[i * 3 + j] = RI[i * 3 + 0] * R[j * 3 + 0] + RI[i * 3 + 1] * R[j * 3 + 1] + RI[i * 3 + 2] * R[j * 3 + 2];
-        const double c00 = Iw[4] * Iw[8] - Iw[5] * Iw[7];
-        const double c01 = Iw[5] * Iw[6] - Iw[3] * Iw[8];
-        const double c02 = Iw[3] * Iw[7] - Iw[4] * Iw[6];
-        const double id = 1.0 / (Iw[0] * c00 + Iw[1] * c01 + Iw[2] * c02);
-        iw[0] = c00 * id;
-        iw[1] = (Iw[2] * Iw[7] - Iw[1] * Iw[8]) * id;
-        iw[2] = (Iw[1] * Iw[5] - Iw[2] * Iw[4]) * id;
-        iw[3] = c01 * id;
-        iw[4] = (Iw[0] * Iw[8] - Iw[2] * Iw[6]) * id;
-        iw[5] = (Iw[2] * Iw[3] - Iw[0] * Iw[5]) * id;
-        iw[6] = c02 * id;
-        iw[7] = (Iw[1] * Iw[6] - Iw[0] * Iw[7]) * id;
-        iw[8] = (Iw[0] * Iw[4] - Iw[1] * Iw[3]) * id;
-        // G0 = dt [I_w^-1 skew(r_j) ; I/m] (ConvexQPSolver.cpp:198-212; Utils.cpp:89-95), terrain: G0 blkdiag(R_j)
+        world_inertia_inv(hdr + LMPC_REC_ROT, prm.Ib, iw);
         for (int e = lane; e < 72; e += 64) {
-            const int r = e / 12, c = e % 12, j = c / 3, cc = c % 3;
-            double w[3];
-            if (r < 3) {
-                const ldouble* ft = hdr + LMPC_REC_FEET + 3 * j;
-                // row r of I_w^-1 by selects (a dynamically indexed private array would live in scratch memory)
-                const double a0 = r == 0 ? iw[0] : r == 1 ? iw[3] : iw[6];
-                const double a1 = r == 0 ? iw[1] : r == 1 ? iw[4] : iw[7];
-                const double a2 = r == 0 ? iw[2] : r == 1 ? iw[5] : iw[8];
-                w[0] = dt * (a1 * ft[2] - a2 * ft[1]);
-                w[1] = dt * (-a0 * ft[2] + a2 * ft[0]);
-                w[2] = dt * (a0 * ft[1] - a1 * ft[0]);
-            } else {
-                w[0] = w[1] = w[2] = 0.0;
-                w[r - 3] = dt / prm.mass;
-            }
-            double v = w[cc];
-            if constexpr (TERRAIN) {
-                const ldouble* Rj = tf + 9 * j;
-                v = w[0] * Rj[cc] + w[1] * Rj[3 + cc] + w[2] * Rj[6 + cc];
-            }
-            G0s[e] = v;
+            // row r of I_w^-1 by selects (a dynamically indexed private array would live in scratch memory)
+            const int r = e / 12;
+            const double a0 = r == 0 ? iw[0] : r == 1 ? iw[3] : iw[6];
+            const double a1 = r == 0 ? iw[1] : r == 1 ? iw[4] : iw[7];
+            const double a2 = r == 0 ? iw[2] : r == 1 ? iw[5] : iw[8];
+            G0s[e] = g0_entry<TERRAIN>(prm, e, a0, a1, a2, hdr, tf);
         }
     }
     LMPC_SYNC();
 
-    // ---- leg-step ownership, starting point (lmpc_kernels.hip) -----------------------------------------------
+    // ---- leg-step ownership, starting point (ipm_start) -------------------------------------------------------
     bool st[LS], valid[LS];
     int lsk[LS], lsj[LS];
     double f[LS][3], s[LS][5], z[LS][5];
@@ -332,16 +279,8 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
         lsj[t] = ls & 3;
         st[t] = valid[t] && contact[(size_t)qp * 4 * H + ls] != 0;
         nst_loc += st[t] ? 1 : 0;
-        f[t][0] = f[t][1] = 0.0;
         const double cnt = quad_sum(st[t] ? 1.0 : 0.0);
-        f[t][2] = st[t] ? fmin(0.5 * fzmax, prm.mass * prm.grav / fmax(cnt, 1.0)) : 0.0;
-        double o[5];
-        cons_resid(f[t], mu, fzmax, o);
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            s[t][i] = st[t] ? -o[i] : 1.0;
-            z[t][i] = 1.0 / s[t][i];
-        }
+        ipm_start(st[t], fmax(cnt, 1.0), prm.mass * prm.grav, mu, fzmax, f[t], s[t], z[t]);
 #pragma unroll
         for (int m = 0; m < 3; ++m) u[t][m] = ua[t][m] = rr[t][m] = 0.0;
 #pragma unroll
@@ -378,12 +317,11 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
                 double loc = 0.0;
 #pragma unroll
                 for (int t = 0; t < LS; ++t)
-                    if (st[t])
-#pragma unroll
-                        for (int i = 0; i < 5; ++i) loc += s[t][i] * z[t][i];
+                    if (st[t]) ipm_gap(s[t], z[t], loc);
                 mu_c = wave_sum(loc) / mc;
                 if (mu_c < tol || ipm_it >= it_end) {
-                    // active set from the interior point: z > LMPC_ACT_RATIO s, lift-off legs -> apex
+                    // active set from the interior point: z > LMPC_ACT_RATIO s, lift-off legs -> apex (the text of
+                    // ipm_guess_active: through the function the <2,true,2> instance spills 4 more VGPRs)
 #pragma unroll
                     for (int t = 0; t < LS; ++t) {
                         act[t] = 0;
@@ -456,22 +394,12 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
                         }
                     } else if (md == PRED) {
                         // interior point: Rr = Rb + C'WC, rr = C'W(s - b) (predictor); identity / zero on swing legs
-                        double W[5] = {0, 0, 0, 0, 0}, wv[5] = {0, 0, 0, 0, 0};
-                        if (st[t]) {
+                        const RecipOf is{s[t]};
+                        ipm_barrier<false>(st[t], s[t], is, z[t], mu, fzmax, rb, Rr[t], rr[t]);
+                        if (!st[t]) {
     #pragma unroll
-                            for (int i = 0; i < 5; ++i) {
-                                W[i] = z[t][i] * rcp_nr(s[t][i]);
-                                wv[i] = W[i] * (s[t][i] - (i == 4 ? fzmax : 0.0));
-                            }
+                            for (int e = 0; e < 6; ++e) Rr[t][e] = (e == 0 || e == 3 || e == 5) ? 1.0 : 0.0;
                         }
-                        const double sx = W[0] + W[1], sy = W[2] + W[3];
-                        Rr[t][0] = st[t] ? rb[0] + sx : 1.0;
-                        Rr[t][1] = st[t] ? rb[1] : 0.0;
-                        Rr[t][2] = st[t] ? rb[2] + mu * (W[0] - W[1]) : 0.0;
-                        Rr[t][3] = st[t] ? rb[3] + sy : 1.0;
-                        Rr[t][4] = st[t] ? rb[4] + mu * (W[2] - W[3]) : 0.0;
-                        Rr[t][5] = st[t] ? rb[5] + mu * mu * (sx + sy) + W[4] : 1.0;
-                        cons_tw(wv, mu, rr[t]);
                     }
                     // (CORR: Rr unchanged; rr was set to the corrector's by the predictor step below)
                     bool cp = false;
@@ -1283,34 +1211,20 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
 #pragma unroll
                     for (int m = 0; m < 3; ++m) ua[t][m] = u[t][m];
                     if (!st[t]) continue;
-                    double o[5];
-                    cons_resid(u[t], mu, fzmax, o);
-#pragma unroll
-                    for (int i = 0; i < 5; ++i) {
-                        dsa[t][i] = -o[i] - s[t][i];
-                        dza[t][i] = -z[t][i] - z[t][i] * rcp_nr(s[t][i]) * dsa[t][i];
-                        if (dsa[t][i] < 0.0) amax = fmin(amax, -s[t][i] * __builtin_amdgcn_rcp(dsa[t][i]));
-                        if (dza[t][i] < 0.0) amax = fmin(amax, -z[t][i] * __builtin_amdgcn_rcp(dza[t][i]));
-                    }
+                    const RecipOf is{s[t]};
+                    ipm_pred_leg(u[t], s[t], is, z[t], mu, fzmax, dsa[t], dza[t], amax);
                 }
                 const double aa = wave_min(amax);
                 double loc = 0.0;
 #pragma unroll
                 for (int t = 0; t < LS; ++t)
-                    if (st[t])
-#pragma unroll
-                        for (int i = 0; i < 5; ++i) loc += (s[t][i] + aa * dsa[t][i]) * (z[t][i] + aa * dza[t][i]);
-                const double ratio = (wave_sum(loc) / mc) / mu_c;
-                smu = ratio * ratio * ratio * mu_c;
-                // corrector linear term rr' = C' w'
+                    if (st[t]) ipm_aff_gap(s[t], z[t], dsa[t], dza[t], aa, loc);
+                smu = ipm_centring((wave_sum(loc) / mc) / mu_c, mu_c);
 #pragma unroll
                 for (int t = 0; t < LS; ++t) {
                     if (!st[t]) continue;
-                    double wv[5];
-#pragma unroll
-                    for (int i = 0; i < 5; ++i)
-                        wv[i] = (z[t][i] * (s[t][i] - (i == 4 ? fzmax : 0.0)) + smu - dsa[t][i] * dza[t][i]) * rcp_nr(s[t][i]);
-                    cons_tw(wv, mu, rr[t]);
+                    const RecipOf is{s[t]};
+                    ipm_corr_rhs(s[t], is, z[t], dsa[t], dza[t], smu, mu, fzmax, rr[t]);
                 }
                 mode = CORR;
                 LQ_STAMP(6);  // predictor step
@@ -1322,24 +1236,13 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
 #pragma unroll
                     for (int i = 0; i < 5; ++i) ds[t][i] = dz[t][i] = 0.0;
                     if (!st[t]) continue;
-                    double o[5], oa[5];
-                    cons_resid(u[t], mu, fzmax, o);
-                    cons_resid(ua[t], mu, fzmax, oa);
-#pragma unroll
-                    for (int i = 0; i < 5; ++i) {
-                        const double is = rcp_nr(s[t][i]);
-                        const double dsa = -oa[i] - s[t][i];
-                        const double dza = -z[t][i] - z[t][i] * is * dsa;
-                        ds[t][i] = -o[i] - s[t][i];
-                        dz[t][i] = (smu - z[t][i] * s[t][i] - dsa * dza - z[t][i] * ds[t][i]) * is;
-                        if (ds[t][i] < 0.0) amax = fmin(amax, -s[t][i] * __builtin_amdgcn_rcp(ds[t][i]));
-                        if (dz[t][i] < 0.0) dmax = fmin(dmax, -z[t][i] * __builtin_amdgcn_rcp(dz[t][i]));
-                    }
+                    const RecipOf is{s[t]};
+                    ipm_corr_leg(u[t], ua[t], s[t], is, z[t], smu, mu, fzmax, ds[t], dz[t], amax, dmax);
                 }
-                const double alpha = fmin(1.0, LMPC_STEP_FRAC * wave_min(amax));
-                const double alpd = fmin(1.0, LMPC_STEP_FRAC * wave_min(dmax));
+                const double alpha = ipm_step_length(wave_min(amax));
+                const double alpd = ipm_step_length(wave_min(dmax));
 #pragma unroll
-                for (int t = 0; t < LS; ++t) {
+                for (int t = 0; t < LS; ++t) {  // (not a shared function: as one, the two-wave instances spill 7 more VGPRs)
                     if (!st[t]) continue;
 #pragma unroll
                     for (int m = 0; m < 3; ++m) f[t][m] += alpha * (u[t][m] - f[t][m]);
@@ -1358,7 +1261,7 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
                 // the forward sweep produced must be the dynamics of the forces returned (x_{k+1} = A_k x_k + B u_k -
                 // g dt e11, every row at once), the adjoint lambda of that trajectory gives the gradient, and every
                 // stance leg-step must then be primal feasible, stationary on its free directions and carry
-                // multipliers of the right sign (lmpc_kernels.hip) ========
+                // multipliers of the right sign (leg_certify) ========
                 bool dyn_ok;  // wave-uniform: the dynamics residual within tol_p of the state scale (max |x|, >= 1)
 #ifdef LMPC_KKT_DIAG
                 double lmpc_kkt_dyn;
@@ -1447,24 +1350,8 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
                     if (!valid[t]) continue;
                     const int j = lsj[t];
                     const ldouble* lam = slots + lsk[t] * LQ_SLOT + LQ_RHO;
-                    double ru[3];
-                    if constexpr (!TERRAIN) {
-#pragma unroll
-                        for (int p = 0; p < 3; ++p) ru[p] = prm.r[3 * j + p] * u[t][p];
-                    } else {
-                        const ldouble* rb = rbt + 6 * j;
-                        ru[0] = rb[0] * u[t][0] + rb[1] * u[t][1] + rb[2] * u[t][2];
-                        ru[1] = rb[1] * u[t][0] + rb[3] * u[t][1] + rb[4] * u[t][2];
-                        ru[2] = rb[2] * u[t][0] + rb[4] * u[t][1] + rb[5] * u[t][2];
-                    }
-#pragma unroll
-                    for (int p = 0; p < 3; ++p) {
-                        double v = ru[p];
-#pragma unroll
-                        for (int m = 0; m < 6; ++m) v += G0s[m * 12 + 3 * j + p] * lam[m];
-                        g[t][p] = v;
-                        gloc = fmax(gloc, fabs(v));
-                    }
+                    if constexpr (!TERRAIN) leg_gradient<true>(prm.r + 3 * j, u[t], G0s, j, lam, g[t], gloc);
+                    else leg_gradient<false>(rbt + 6 * j, u[t], G0s, j, lam, g[t], gloc);
                 }
                 const double gscale = wave_max(gloc);
                 int changed = 0;
@@ -1472,35 +1359,16 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
 #pragma unroll
                 for (int t = 0; t < LS; ++t) {
                     if (!st[t]) continue;
-                    double o[5];
-                    cons_resid(u[t], mu, fzmax, o);
-                    int imax = -1;
-                    double vmax = prm.tol_p * fzmax;
-#pragma unroll
-                    for (int i = 0; i < 5; ++i)
-                        if (!((act[t] >> i) & 1) && o[i] > vmax) {
-                            vmax = o[i];
-                            imax = i;
-                        }
-                    if (imax >= 0) {
+                    const int imax = leg_violated(u[t], act[t], mu, fzmax, prm.tol_p * fzmax);
+                    if (imax >= 0) {  // a violated face enters first, the most violated one
                         act[t] |= 1 << imax;
                         changed = 1;
                         continue;
                     }
-                    if (apex[t]) {  // the cone test is the whole certificate at the apex (f = 0, every direction bound)
-                        if (g[t][2] / mu < fabs(g[t][0]) + fabs(g[t][1]) - prm.tol_d * gscale) {
-                            act[t] = (g[t][0] < 0.0 ? 2 : 1) | (g[t][1] < 0.0 ? 8 : 4);
-                            changed = 1;
-                        }
-                        continue;
-                    }
-                    // (act = 0: no multipliers, the residual is g itself)
-                    const LegKkt kk = leg_kkt(act[t], g[t], mu, -prm.tol_d * gscale);
-                    if (kk.drop >= 0) {
-                        act[t] &= ~(1 << kk.drop);
-                        changed = 1;
-                    }
-                    sres = fmax(sres, kk.res);
+                    const LegCert c = leg_certify_dual(g[t], act[t], apex[t], mu, prm.tol_d * gscale);
+                    act[t] = c.act;
+                    if (c.changed) changed = 1;
+                    sres = fmax(sres, c.res);
                 }
                 LQ_STAMP(9);  // polish verification
                 if (!__any(changed)) {
@@ -1530,9 +1398,7 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
                     rd = prm.max_rounds - 1;
                 }
                 if (++rd >= prm.max_rounds) {
-                    if (++att >= prm.max_attempts) break;
-                    tol = retry_tol(tol, att);
-                    it_end += prm.max_iter;
+                    if (!ipm_retry(prm, att, tol, it_end)) break;
                     mode = PRED;
                 }
             }
@@ -1547,30 +1413,8 @@ __device__ __forceinline__ void lq_body(const DevParams prm, const double* __res
 #pragma unroll
             for (int m = 0; m < 3; ++m) u[t][m] = f[t][m];
     }
-    // ---- NaN guard (reference: NaN -> zeros, ConvexQPSolver.cpp:321-326) and output ----
-    int bad = 0;
-#pragma unroll
-    for (int t = 0; t < LS; ++t)
-        if (valid[t]) bad |= (u[t][0] != u[t][0] || u[t][1] != u[t][1] || u[t][2] != u[t][2]) ? 1 : 0;
-    const bool anybad = __any(bad);
-    double* gout = grf + (size_t)qp * 12 * H;
-#pragma unroll
-    for (int t = 0; t < LS; ++t) {
-        if (!valid[t]) continue;
-        const int ls = lane + 64 * t;
-        double fo[3] = {u[t][0], u[t][1], u[t][2]};
-        if constexpr (TERRAIN) {
-            const ldouble* Rj = tf + 9 * lsj[t];
-#pragma unroll
-            for (int p = 0; p < 3; ++p) fo[p] = Rj[3 * p] * u[t][0] + Rj[3 * p + 1] * u[t][1] + Rj[3 * p + 2] * u[t][2];
-        }
-#pragma unroll
-        for (int p = 0; p < 3; ++p) gout[3 * ls + p] = (anybad || !st[t]) ? 0.0 : fo[p];
-    }
-    if (lane == 0) {
-        if (status) status[qp] = anybad ? LMPC_QP_NAN : qstatus;
-        if (iters) iters[qp] = ipm_it | (prounds << 16);
-    }
+    const bool anybad = qp_store_forces<LS, TERRAIN>(valid, st, lsj, u, tf, grf + (size_t)qp * 12 * H, lane);
+    qp_store_words(status, iters, qp, lane, anybad, qstatus, ipm_it, prounds);
     LQ_STAMP(10);
     LQ_STAMP_FLUSH(qp);
 }
